@@ -3,9 +3,16 @@
 the engine's async decoding scheduler (BASELINE.json configs[1]), plus the HBM roofline of the
 dominant hot-path kernel (paged_attention_v2's pass over the paged KV cache) and CPU baselines.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
       N > 1: launched by the driver through torch.distributed.run, or -- started as one plain process --
       launching its own N ranks that way (one rank per GPU, independent replicas)
+
+A plain run does what the headline needs and no more: set-up, W warm-up steps, ONE timed region of exactly K model
+steps, the output files of --dump-outputs, the result line with the headline fields (metric, value, unit, ms_per_step,
+dtype, config, timed_regions ...).  --full adds every other measurement behind it, each with a run of its own: the region
+at more steps in flight, the kernel rooflines (attention, projections, prefill), the CPU and per-operator baselines,
+BASELINE configs 3 / 4 / 5 and sampled decode (`other_settings`), and, for short regions, repeated regions with the
+median reported.
 
 A "step" is one MODEL step: 32 decoding sequences go through the 32-layer forward, lm_head and greedy
 arg-max (a captured HIP graph) and get one token each.  The scheduler admits one batch of 32 per engine step
@@ -17,8 +24,8 @@ holds exactly K model steps with an empty pipeline on both sides.  Every rank is
 own weights, KV cache and scheduler (replicas only, no collective on the data path); `value`
 is the sum over ranks.
 
-Output: ONE JSON line on rank 0 (contract in the task description; roofline / cpu_baseline / ops_baseline /
-other_settings objects described in DESIGN.md section 5).
+Output: ONE JSON line on rank 0 (the roofline / cpu_baseline / ops_baseline / other_settings objects of a --full run
+are described in DESIGN.md section 5).
 """
 import argparse
 import ctypes
@@ -47,6 +54,16 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=64)
     ap.add_argument("--warmup", type=int, default=16)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline region also run everything else the script measures (more steps in flight, "
+                         "kernel rooflines, CPU and per-operator baselines, BASELINE configs 3 / 4 / 5, sampled decode) and "
+                         "report it beside the headline; without it the run sets up, warms up, times --steps model steps "
+                         "and prints the headline fields only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what they produced as DIR/<name>.npy (float32): `tokens` = the output "
+                         "token ids of every request, one row each in request order, -1 behind a shorter row; "
+                         "`last_hidden` = the final hidden state of every request's last model step (HIP graph runs only). "
+                         "Inputs are seeded: the same arguments give the same files")
     ap.add_argument("--batch-size", type=int, default=32)
     ap.add_argument("--context", type=int, default=1024)
     ap.add_argument("--scheduling", default="async", choices=["sync", "simple_async", "async", "double_buffer"],
@@ -97,9 +114,9 @@ def parse():
                     help="no roofline_prefill object (one 16k-token prompt through the prefill kernel)")
     ap.add_argument("--repeats", type=int, default=0,
                     help="the timed region (EXACTLY --steps model steps, barrier + synchronize on both sides) is run this "
-                         "many times back to back and `value` is the MEDIAN region; 0 = auto: min(5, 100 // steps), i.e. "
-                         "one region at the default 64 steps, five when a caller passes --steps 20 (a 68 ms region moves "
-                         "+-1 % from run to run)")
+                         "many times back to back and `value` is the MEDIAN region; 0 = auto: one region, so that --steps is "
+                         "the number of timed steps of the run; with --full min(5, 100 // steps), i.e. one region at the "
+                         "default 64 steps, five when a caller passes --steps 20 (a 68 ms region moves +-1 %% from run to run)")
     ap.add_argument("--no-pin", action="store_true", help="N > 1: do not pin the rank to its GPU's NUMA cores")
     ap.add_argument("--kernel-iters", type=int, default=224)  # 20 warm-up + 200 timed launches
     ap.add_argument("--tiny", action="store_true", help="tiny model (plumbing check)")
@@ -806,6 +823,45 @@ def largest_divisor_at_most(n, k):
     return 1
 
 
+def dump_outputs(engine, out_dir, rank=0):
+    """--dump-outputs: what the timed path handed back, as float32 .npy files a second build can be compared against.
+    `tokens` [requests, longest output]: every request's output token ids in request order (the ids a caller of
+    LLMEngine.async_step receives; the first is the synthetic prefill's, the last ones the timed region's last steps),
+    -1 behind the end of a shorter row.  `last_hidden` [requests, hidden]: the hidden state the lm_head's arg-max read at
+    each request's last model step, taken from the static output of the slot's captured graph (rows are matched to
+    requests by the first block of their block table); not written without HIP graphs.  Rank r > 0 writes
+    <name>.rank<r>.npy."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = "" if rank == 0 else f".rank{rank}"
+    groups = sorted(engine.groups.values(), key=lambda g: int(g.request_id))
+    outs = [list(g.seqs[0].get_output_token_ids()) for g in groups]
+    tokens = np.full((len(outs), max(len(o) for o in outs)), -1.0, dtype=np.float32)
+    for i, o in enumerate(outs):
+        tokens[i, :len(o)] = o
+    np.save(os.path.join(out_dir, f"tokens{suffix}.npy"), tokens)
+    pools = engine.worker.graph_pools
+    if pools is None:
+        return
+    torch.cuda.synchronize(engine.device)
+    bm = engine.scheduler.block_manager
+    row_of = {bm.get_block_table(g.seqs[0])[0]: i for i, g in enumerate(groups)}
+    hidden = np.zeros((len(groups), engine.model_config.hidden_size), dtype=np.float32)
+    newest = [0] * len(groups)  # a request may have rows in several slots' graphs: its longest context is its last step
+    for pool in pools:
+        for graph in pool.graphs.values():
+            if graph.hidden is None:
+                continue
+            h = graph.hidden.float().cpu().numpy()
+            first = graph.block_tables[:, 0].tolist()
+            lens = graph.seq_lens.tolist()
+            for r in range(graph.batch_size):
+                i = row_of.get(first[r])
+                if i is not None and lens[r] > newest[i]:
+                    hidden[i], newest[i] = h[r], lens[r]
+    np.save(os.path.join(out_dir, f"last_hidden{suffix}.npy"), hidden)
+
+
 def spawn_replicas(a):
     """`python bench.py --gpus N` started as ONE plain process: start the N ranks itself, before anything in this
     process touches a GPU -- a child `python -m torch.distributed.run` (the launcher the driver uses), whose exit
@@ -864,7 +920,7 @@ def main():
     B, ctx = a.batch_size, a.context
     k, kw, on_the_fly = plan_steps(a)
     k_max = max(k, kw)
-    extra = a.also_on_the_fly if (a.scheduling != "sync" and a.also_on_the_fly > on_the_fly
+    extra = a.also_on_the_fly if (a.full and a.scheduling != "sync" and a.also_on_the_fly > on_the_fly
                                   and a.steps // k >= a.also_on_the_fly) else 0
     slots = max(on_the_fly, extra)
     n_req = B * on_the_fly
@@ -877,7 +933,7 @@ def main():
     if a.o_proj_partials_min_rows is not None:
         cfg.o_proj_partials_min_rows = a.o_proj_partials_min_rows
     cfg.quantization = a.quantization
-    reps = a.repeats if a.repeats > 0 else max(1, min(5, 100 // max(1, a.steps)))
+    reps = a.repeats if a.repeats > 0 else (max(1, min(5, 100 // max(1, a.steps))) if a.full else 1)
     total_steps = a.steps * reps + a.warmup
     reps_extra = min(reps, 3)  # regions of the more-in-flight leg (median reported, like the headline's)
     max_len = ctx + total_steps // on_the_fly + ((a.steps + 3 * k_max) * reps_extra + 2 * k) // max(1, slots) + 2 * k_max + 8
@@ -953,6 +1009,9 @@ def main():
         el = group.max(el)                          # slowest replica's clock
         regions.append((group.sum(tokens) / el, el))  # whole-job tokens/s of this region
     value, elapsed = sorted(regions)[len(regions) // 2]
+    if a.dump_outputs:
+        dump_outputs(engine, a.dump_outputs, rank)
+    # Everything below the headline region runs with --full only.
     # More steps in flight (a SchedulerConfig setting of the reference; BASELINE.md quotes the headline at 2): B more
     # sequences per extra step are admitted at the same context, one burst per slot warms the new pipeline depth,
     # then the same number of model steps is timed again.  Reported beside the headline, never as `value`.
@@ -985,16 +1044,16 @@ def main():
                                                 "note": "regions of whole rounds of bursts (steps = a multiple of burst x "
                                                         "steps in flight): a region that ends with fewer bursts than the "
                                                         "pipeline is deep runs them at the single-stream rate"}
-    kl = kernel_leg(engine, B, a.kernel_iters, seq_len=ctx)
-    in_step = in_step_attention_leg(engine, B, ctx) if rank == 0 else None
-    gm = gemm_leg(engine, B) if B <= 64 else None
+    kl = kernel_leg(engine, B, a.kernel_iters, seq_len=ctx) if a.full else None
+    in_step = in_step_attention_leg(engine, B, ctx) if a.full and rank == 0 else None
+    gm = gemm_leg(engine, B) if a.full and B <= 64 else None
     cpu = ops_base = None
-    if rank == 0 and world == 1 and not a.skip_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.skip_cpu_baseline:
         cpu = cpu_baseline_leg(engine, B)
-    if rank == 0 and world == 1 and not a.skip_ops_baseline:
+    if a.full and rank == 0 and world == 1 and not a.skip_ops_baseline:
         ops_base = ops_baseline_leg(engine, B)
     pf = None
-    if rank == 0 and world == 1 and not a.skip_prefill_roofline and not a.tiny:
+    if a.full and rank == 0 and world == 1 and not a.skip_prefill_roofline and not a.tiny:
         pf = prefill_leg(engine)
     ctx_end = sum(s.get_len() for grp in engine.scheduler.running for s in grp.seqs) / max(1, len(engine.scheduler.running))
     # HBM traffic per launch from the PMC passes committed under profiles/ (rocprofv3 --pmc FETCH_SIZE and
@@ -1004,12 +1063,12 @@ def main():
     try:
         pmc_attn = "r03_pmc_attn_fp8.json" if a.kv_cache_dtype != "auto" else "r03_pmc_attn.json"
         with open(os.path.join(ROOT, "profiles", pmc_attn)) as f:
-            traffic = int(json.load(f)["traffic_over_algorithmic"] * kl["algo_bytes"])
+            traffic = int(json.load(f)["traffic_over_algorithmic"] * kl["algo_bytes"]) if kl is not None else None
     except (OSError, KeyError, ValueError):
         pass
     engine.shutdown()
     # BASELINE configs 3, 4, 5 beside the headline (never as `value`): each on its own engine, after this one is gone
-    if (rank == 0 and world == 1 and not a.skip_other_configs and a.scheduling == "async"
+    if (a.full and rank == 0 and world == 1 and not a.skip_other_configs and a.scheduling == "async"
             and not (a.quantization or a.kv_cache_dtype != "auto")):
         import gc
         engine.worker.graph_pools = None
@@ -1024,7 +1083,6 @@ def main():
             gc.collect()
             torch.cuda.empty_cache()
     if rank == 0:
-        achieved = kl["algo_bytes"] / kl["avg_s"] / 1e9
         line = {
             "metric": "decode tokens/sec Llama-3-8B bs=32 seq=1k; paged-attn HBM GB/s vs roofline",
             "value": round(value, 1), "unit": "tokens/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
@@ -1046,21 +1104,24 @@ def main():
                        "num_scheduler_steps": k, "max_num_on_the_fly": on_the_fly},
             "timed_regions": {"count": reps, "value": "median", "tokens_per_s": [round(v, 1) for v, _ in regions],
                               "ms_per_step": [round(e / a.steps * 1e3, 4) for _, e in regions]},
-            "roofline": {"bound": "hbm", "kernel": "paged_attention_v2 (paged_attn_mfma_kernel): "
-                                                      + ("single pass, nsplit = 1 -- the batch alone fills the GPU, no "
-                                                         "reduce launch, scratch untouched" if kl["nsplit"] == 1 else
-                                                         f"partition pass, {kl['nsplit']} shares per context") +
-                                                      f"; seq_lens = {ctx} for all {B} sequences",
-                         "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
-                         "traffic_source": "profiles/r03_pmc_attn[_fp8].json (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE in "
-                                           "separate passes of the same kernel at seq = 1024: 2*FETCH_SIZE + WRITE_SIZE per "
-                                           "launch, scaled by this launch's algorithmic bytes; a recording, not this run)",
-                         "algorithmic_bytes_per_launch": kl["algo_bytes"],
-                         "avg_launch_us": round(kl["avg_s"] * 1e6, 2), "min_launch_us": round(kl["min_s"] * 1e6, 2),
-                         "in_step": in_step},
-            "cpu_baseline": cpu,
         }
+        if a.full:
+            achieved = kl["algo_bytes"] / kl["avg_s"] / 1e9
+            line["roofline"] = {
+                "bound": "hbm", "kernel": "paged_attention_v2 (paged_attn_mfma_kernel): "
+                                          + ("single pass, nsplit = 1 -- the batch alone fills the GPU, no "
+                                             "reduce launch, scratch untouched" if kl["nsplit"] == 1 else
+                                             f"partition pass, {kl['nsplit']} shares per context") +
+                                          f"; seq_lens = {ctx} for all {B} sequences",
+                "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
+                "traffic_source": "profiles/r03_pmc_attn[_fp8].json (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE in "
+                                  "separate passes of the same kernel at seq = 1024: 2*FETCH_SIZE + WRITE_SIZE per "
+                                  "launch, scaled by this launch's algorithmic bytes; a recording, not this run)",
+                "algorithmic_bytes_per_launch": kl["algo_bytes"],
+                "avg_launch_us": round(kl["avg_s"] * 1e6, 2), "min_launch_us": round(kl["min_s"] * 1e6, 2),
+                "in_step": in_step}
+            line["cpu_baseline"] = cpu
         if world > 1:
             line["affinity_rank0"] = pin
         if other:

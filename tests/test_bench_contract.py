@@ -67,7 +67,8 @@ def test_gpus_n_started_as_one_process_launches_n_ranks(monkeypatch):
     assert seen["env"]["HSA_ENABLE_IPC_MODE_LEGACY"] == "0"
 
 
-def check_line(d, batch):
+def check_line(d, batch, full=True):
+    """`full`: the line of a `--full` run (or a recording of one), which carries the roofline object as well."""
     with open(os.path.join(ROOT, "BASELINE.json")) as f:
         base = json.load(f)
     assert d["metric"] == base["metric"]
@@ -79,6 +80,8 @@ def check_line(d, batch):
     # value = tokens of all ranks / time; ms_per_step is per MODEL step whatever the burst length
     assert abs(d["value"] - batch * d["n_gpus"] / (d["ms_per_step"] * 1e-3)) / d["value"] < 2e-3
     assert d["steps"] % d["config"]["num_scheduler_steps"] == 0
+    if not full:
+        return
     r = d["roofline"]
     assert r["bound"] == "hbm" and r["unit"] == "GB/s" and r["peak"] == 8000.0
     assert abs(r["frac"] - r["achieved"] / r["peak"]) < 1e-3
@@ -105,10 +108,10 @@ def test_recorded_bench_lines_have_the_contract_fields():
 @pytest.mark.parametrize("extra", [[], ["--kv-cache-dtype", "fp8"], ["--num-scheduler-steps", "1", "--scheduling", "sync"]],
                          ids=["default", "fp8_kv", "single_step_sync"])
 def test_bench_runs_end_to_end_on_a_tiny_model(extra):
-    """The whole script -- engine, bursts, ctypes kernel leg (16-bit and fp8 caches), GEMM leg, per-op baselines --
-    in a child process on the tiny model; the line it prints satisfies the contract."""
+    """The whole script (`--full`) -- engine, bursts, ctypes kernel leg (16-bit and fp8 caches), GEMM leg, per-op
+    baselines -- in a child process on the tiny model; the line it prints satisfies the contract."""
     env = dict(os.environ)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--tiny", "--steps", "24", "--warmup", "8",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--tiny", "--steps", "24", "--warmup", "8",
                         "--batch-size", "8", "--context", "64", "--kernel-iters", "64"] + extra,
                        capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -152,13 +155,40 @@ def test_bench_runs_end_to_end_on_a_tiny_model(extra):
 
 
 @pytest.mark.gpu
+def test_plain_run_times_the_steps_and_nothing_else_and_dumps_its_outputs(tmp_path):
+    """Without `--full`: one timed region of exactly --steps model steps, the headline fields, none of the objects
+    that take runs of their own; `--dump-outputs` leaves the tokens of every request and the last hidden states
+    as float32 arrays."""
+    import numpy as np
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--tiny", "--steps", "24", "--warmup", "8",
+                        "--batch-size", "8", "--context", "64", "--dump-outputs", str(out)],
+                       capture_output=True, text=True, timeout=600, env=dict(os.environ))
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    check_line(line, 8, full=False)
+    assert line["steps"] == 24 and line["warmup"] == 8 and line["dtype"] == "bf16" and line["unit"] == "tokens/s"
+    tr = line["timed_regions"]
+    assert tr["count"] == 1 and tr["ms_per_step"] == [line["ms_per_step"]] and tr["tokens_per_s"] == [line["value"]]
+    for moved in ("roofline", "cpu_baseline", "ops_baseline", "other_settings", "roofline_prefill", "roofline_projections"):
+        assert moved not in line, moved
+    assert sorted(p.name for p in out.iterdir()) == ["last_hidden.npy", "tokens.npy"]
+    tokens, hidden = np.load(out / "tokens.npy"), np.load(out / "last_hidden.npy")
+    # 2 batches of 8 in flight; 32 model steps + the prefill's token = 16 + 1 tokens per request, 17 x 16 in all
+    assert tokens.dtype == np.float32 and tokens.shape[0] == 16 and (tokens >= 0).sum() == 16 * 17
+    assert ((tokens == -1) | ((tokens >= 0) & (tokens == np.floor(tokens)))).all()
+    assert hidden.dtype == np.float32 and hidden.shape[0] == 16 and np.isfinite(hidden).all()
+    assert (np.abs(hidden).max(axis=1) > 0).all()  # every request's row was found in a slot's graph
+
+
+@pytest.mark.gpu
 def test_bench_gpus_2_launches_its_ranks_and_sums_them():
     """`python bench.py --gpus 2` as ONE plain process: it starts two ranks through torch.distributed.run, they
     meet at the barriers, the slowest clock and the summed tokens make one line with n_gpus = 2.  On a one-GPU box
     both ranks share cuda:0 and the process group is gloo (RCCL refuses two ranks on one device); everything else
     is the path the driver's multi-GPU run takes."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--tiny", "--steps", "16",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full", "--tiny", "--steps", "16",
                         "--warmup", "8", "--batch-size", "8", "--context", "64", "--kernel-iters", "64",
                         "--replica-backend", "gloo", "--single-device"],
                        capture_output=True, text=True, timeout=900, env=env)

@@ -26,7 +26,7 @@ echo "== bench.py --skip-other-configs (value, ms per step, roofline of the atte
 for round in 1 2; do
   for pad in 0 1024; do
     echo "-- block_pad_bytes $pad (round $round)" >> $O
-    timeout -k 10 400 python bench.py --skip-other-configs --kv-block-pad-bytes $pad 2>/dev/null | python -c "
+    timeout -k 10 400 python bench.py --full --skip-other-configs --kv-block-pad-bytes $pad 2>/dev/null | python -c "
 import json,sys
 d=json.loads([l for l in sys.stdin if l.startswith('{')][-1])
 r=d['roofline']

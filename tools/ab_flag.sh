@@ -4,7 +4,7 @@ cd "$(dirname "$0")/.."
 n=$1; shift
 for i in $(seq $n); do
   for f in "" "$*"; do
-    python bench.py --skip-cpu-baseline --skip-ops-baseline --skip-prefill-roofline --steps 128 $f 2>/dev/null > /tmp/ab_flag.json
+    python bench.py --full --skip-cpu-baseline --skip-ops-baseline --skip-prefill-roofline --steps 128 $f 2>/dev/null > /tmp/ab_flag.json
     python - "$f" <<'PY'
 import json, sys
 d = json.loads(open("/tmp/ab_flag.json").read().strip().splitlines()[-1])

@@ -6,7 +6,7 @@ cd "$(dirname "$0")/.."
 v=$1; n=${2:-2}; shift; shift
 O=gpurun_out/ab_variant_$v.txt; : > $O
 cp light-vllm_amd/lib/liblvllm_hip.so /tmp/liblvllm_hip.orig.so
-F="--skip-cpu-baseline --skip-ops-baseline --skip-prefill-roofline --skip-other-configs --steps 128 --warmup 16 $*"
+F="--full --skip-cpu-baseline --skip-ops-baseline --skip-prefill-roofline --skip-other-configs --steps 128 --warmup 16 $*"
 line() { python -c "
 import json,sys
 d=json.loads([l for l in sys.stdin.read().strip().splitlines() if l.startswith('{')][-1])

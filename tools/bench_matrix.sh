@@ -1,7 +1,7 @@
 # The bench line of the tree and its A/B settings, one box (numbers of different boxes differ by +-3 %).
 ulimit -c 0
 O=gpurun_out/r02_matrix; mkdir -p $O
-run() { name=$1; shift; timeout -k 10 300 python bench.py "$@" > $O/$name.json 2> $O/$name.err || { echo "$name: bench.py did not finish (exit $?)"; return 0; }; python -c "
+run() { name=$1; shift; timeout -k 10 300 python bench.py --full "$@" > $O/$name.json 2> $O/$name.err || { echo "$name: bench.py did not finish (exit $?)"; return 0; }; python -c "
 import json; d=json.loads(open('$O/$name.json').read().strip().splitlines()[-1])
 o=d.get('other_settings',{})
 print('%-24s %8.1f tok/s  %.4f ms/step  (%d in flight)   %s' % ('$name', d['value'], d['ms_per_step'], d['config']['max_num_on_the_fly'], '  '.join('%s: %s' % (k.replace('max_num_on_the_fly=', 'in flight '), v['value']) for k, v in o.items())))"; }
