@@ -547,6 +547,36 @@ int lvllm_rope_cache_paged_attention_q(
     int64_t key_stride, int64_t value_stride, int64_t kv_block_stride, int64_t kv_head_stride, int dtype,
     int kv_dtype, float k_scale, float v_scale, int64_t kv_cache_bytes, void* stream);
 
+/* ---- W4A16: AWQ int4 group-quantised weights, 16-bit activations (csrc/awq_gemm.hip) -------------------------
+ * Checkpoint tensors as the reference holds them (awq.py:103-151, quant_utils.py:374-391): qweight int32 [K, N/8],
+ * qzeros int32 [K/G, N/8], scales T [K/G, N]; nibble i of word j is column 8 j + [0,2,4,6,1,3,5,7][i]
+ * (dequantize.cuh:41-61), values unsigned.  Wd[k, n] = T(float(q - z) * float(s)), one rounding: the bits of the
+ * reference's sub.f16x2 + fma.rn.f16x2 (gemm_kernels.cu:372-401); bf16 is defined the same way.
+ *
+ * lvllm_awq_pack: once, after loading -- the checkpoint tensors in the order the streaming kernel reads:
+ * w4_packed = lvllm_awq_packed_bytes(N, K) bytes, [N/16][Kp/128][lane 64][16 bytes], meta =
+ * lvllm_awq_meta_bytes(N, K, G) bytes, [N/16][Kp/128][16][128/G] words {T scale, T(zero)}; Kp = K rounded up to 128
+ * (padding dequantises to 0).  N % 16 == 0, G in {32, 64, 128}, K % G == 0, packed weight below 4 GiB.
+ * lvllm_awq_dequantize: out [K, N] T = Wd from the checkpoint tensors (ops.awq_dequantize, gemm_kernels.cu:413-418),
+ * N % 8 == 0.  lvllm_awq_dequantize_packed: the same from the packed pair (the route above 64 rows, where the
+ * reference dequantises and calls the library GEMM as well: awq.py:164-169).
+ * lvllm_skinny_gemm_w4a16: y [M, N] = T(x . Wd (+ bias)), fp32 accumulation, x [M <= 64, K] (rows ldx elements
+ * apart) -- ops.awq_gemm (gemm_kernels.cu:469-471) for decode batches.  K % 128 == 0 in addition to the conditions
+ * of lvllm_awq_pack; returns 3 and launches nothing outside the envelope.  workspace: fp32 split-K partials,
+ * lvllm_skinny_gemm_w4a16_workspace_bytes(M, N, K) bytes (0 when K fits one workgroup). */
+int64_t lvllm_awq_packed_bytes(int N, int K);
+int64_t lvllm_awq_meta_bytes(int N, int K, int group_size);
+int lvllm_awq_pack(void* w4_packed, void* meta, const void* qweight, const void* qzeros, const void* scales, int N,
+                   int K, int group_size, int dtype, void* stream);
+int lvllm_awq_dequantize(void* out, const void* qweight, const void* qzeros, const void* scales, int N, int K,
+                         int group_size, int dtype, void* stream);
+int lvllm_awq_dequantize_packed(void* out, const void* w4_packed, const void* meta, int N, int K, int group_size,
+                                int dtype, void* stream);
+int64_t lvllm_skinny_gemm_w4a16_workspace_bytes(int M, int N, int K);
+int lvllm_skinny_gemm_w4a16(void* y, const void* x, const void* w4_packed, const void* meta, const void* bias, int M,
+                            int N, int K, int group_size, int64_t ldx, int dtype, void* workspace,
+                            int64_t workspace_bytes, void* stream);
+
 /* ---- device queries (csrc/cuda_utils.h, torch_bindings.cpp:271-279) ------- */
 int64_t lvllm_get_device_attribute(int64_t attribute, int64_t device_id);
 int64_t lvllm_get_max_shared_memory_per_block_device_attribute(int64_t device_id);

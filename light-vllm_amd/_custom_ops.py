@@ -126,6 +126,21 @@ def scaled_fp8_quant(input: torch.Tensor, scale: Optional[torch.Tensor] = None,
     return output, scale
 
 
+def awq_dequantize(qweight: torch.Tensor, scales: torch.Tensor, zeros: torch.Tensor, split_k_iters: int,
+                   thx: int, thy: int) -> torch.Tensor:
+    """[K, N] dequantised weight of an AWQ checkpoint (_custom_ops.py:181-185 of the reference; the three
+    integers are launch hints of its kernel and are ignored here)."""
+    return _C.awq_dequantize(qweight, scales, zeros, split_k_iters, thx, thy)
+
+
+def awq_gemm(input: torch.Tensor, qweight: torch.Tensor, qzeros: torch.Tensor, scales: torch.Tensor,
+             split_k_iters: int) -> torch.Tensor:
+    """input . dequantised weight on checkpoint-layout tensors (_custom_ops.py:188-190 of the reference, which
+    forwards its arguments by position: its caller passes the scales third and the zeros fourth, awq.py:171-172).
+    Repacks on every call; quantization.pack_awq_weight + apply_awq_linear is the fast path."""
+    return _C.awq_gemm(input, qweight, qzeros, scales, split_k_iters)
+
+
 def advance_step(num_seqs: int, num_queries: int, block_size: int, input_tokens: torch.Tensor,
                  sampled_token_ids: torch.Tensor, input_positions: torch.Tensor, seq_lens: torch.Tensor,
                  slot_mapping: torch.Tensor, block_tables: torch.Tensor) -> None:

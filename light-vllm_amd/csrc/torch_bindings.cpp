@@ -1108,6 +1108,108 @@ torch::Tensor pack_weight(const torch::Tensor& w) {
   return out;
 }
 
+// ---- W4A16 (AWQ): csrc/quantization/awq/gemm_kernels.cu:413-471, awq.py:153-175 of the reference ----
+// N, K and the group size as the checkpoint tensors imply them: qweight [K, N/8], qzeros [K/G, N/8], scales [K/G, N]
+struct AwqShape { int64_t N, K, G; };
+AwqShape awq_shape(const torch::Tensor& qweight, const torch::Tensor& qzeros, const torch::Tensor& scales,
+                   const char* op) {
+  LV_CHECK_DEVICE(qweight);
+  LV_CHECK_DEVICE(qzeros);
+  LV_CHECK_DEVICE(scales);
+  TORCH_CHECK(qweight.scalar_type() == at::kInt && qzeros.scalar_type() == at::kInt &&
+                  (scales.scalar_type() == at::kHalf || scales.scalar_type() == at::kBFloat16),
+              op, ": int32 qweight / qzeros and f16 / bf16 scales");
+  TORCH_CHECK(qweight.dim() == 2 && qzeros.dim() == 2 && scales.dim() == 2 && qweight.is_contiguous() &&
+                  qzeros.is_contiguous() && scales.is_contiguous(),
+              op, ": contiguous 2-D checkpoint tensors");
+  const int64_t K = qweight.size(0), N = scales.size(1), groups = scales.size(0);
+  TORCH_CHECK(K > 0 && N > 0 && groups > 0 && qweight.size(1) * 8 == N && qzeros.size(0) == groups &&
+                  qzeros.size(1) * 8 == N && K % groups == 0,
+              op, ": qweight [K, N/8], qzeros [K/G, N/8], scales [K/G, N]");
+  return {N, K, K / groups};
+}
+
+std::tuple<torch::Tensor, torch::Tensor> awq_pack(const torch::Tensor& qweight, const torch::Tensor& qzeros,
+                                                  const torch::Tensor& scales) {
+  const AwqShape s = awq_shape(qweight, qzeros, scales, "awq_pack");
+  const int64_t wbytes = lvllm_awq_packed_bytes((int)s.N, (int)s.K), mbytes = lvllm_awq_meta_bytes((int)s.N, (int)s.K, (int)s.G);
+  TORCH_CHECK(s.N % 16 == 0 && mbytes > 0, "awq_pack: N % 16 == 0 and a group size of 32, 64 or 128");
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(device_of(qweight));
+  auto w4 = torch::empty({wbytes / 4}, qweight.options());
+  auto meta = torch::empty({mbytes / 4}, qweight.options());
+  check(lvllm_awq_pack(w4.data_ptr(), meta.data_ptr(), qweight.data_ptr(), qzeros.data_ptr(), scales.data_ptr(),
+                       (int)s.N, (int)s.K, (int)s.G, dtype_code(scales, "awq_pack"), current_stream(qweight)));
+  return {w4, meta};
+}
+
+torch::Tensor awq_dequantize(const torch::Tensor& qweight, const torch::Tensor& scales, const torch::Tensor& qzeros,
+                             int64_t split_k_iters, int64_t thx, int64_t thy) {
+  const AwqShape s = awq_shape(qweight, qzeros, scales, "awq_dequantize");
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(device_of(qweight));
+  auto out = torch::empty({s.K, s.N}, scales.options());
+  check(lvllm_awq_dequantize(out.data_ptr(), qweight.data_ptr(), qzeros.data_ptr(), scales.data_ptr(), (int)s.N,
+                             (int)s.K, (int)s.G, dtype_code(scales, "awq_dequantize"), current_stream(qweight)));
+  return out;
+}
+
+// y [M, N] = x . Wd (+ bias) from the packed pair of awq_pack: the streaming kernel at <= 64 rows of its envelope,
+// otherwise Wd from the packed pair and the library GEMM, as the reference does for large batches (awq.py:164-169)
+torch::Tensor skinny_linear_w4a16(const torch::Tensor& x, const torch::Tensor& w4_packed, const torch::Tensor& meta,
+                                  int64_t N, int64_t K, int64_t group_size, const std::optional<torch::Tensor>& bias) {
+  LV_CHECK_DEVICE(x);
+  LV_CHECK_DEVICE(w4_packed);
+  LV_CHECK_DEVICE(meta);
+  TORCH_CHECK(x.dim() == 2 && x.size(1) == K && x.stride(1) == 1 &&
+                  (x.scalar_type() == at::kHalf || x.scalar_type() == at::kBFloat16),
+              "skinny_linear_w4a16: x must be [M, K] f16 / bf16");
+  TORCH_CHECK(N > 0 && K > 0 && N % 16 == 0 && (group_size == 32 || group_size == 64 || group_size == 128) &&
+                  K % group_size == 0,
+              "skinny_linear_w4a16: N % 16 == 0, group_size 32 / 64 / 128, K % group_size == 0");
+  TORCH_CHECK(w4_packed.is_contiguous() && meta.is_contiguous() &&
+                  w4_packed.numel() * w4_packed.element_size() == lvllm_awq_packed_bytes((int)N, (int)K) &&
+                  meta.numel() * meta.element_size() == lvllm_awq_meta_bytes((int)N, (int)K, (int)group_size),
+              "skinny_linear_w4a16: w4_packed / meta do not have the size awq_pack gives for this N, K, group_size");
+  TORCH_CHECK(!bias || (bias->is_cuda() && bias->is_contiguous() && bias->numel() == N &&
+                        bias->scalar_type() == x.scalar_type()),
+              "skinny_linear_w4a16: bias must be [N] of x's dtype");
+  const int64_t M = x.size(0);
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(device_of(x));
+  const int dt = dtype_code(x, "skinny_linear_w4a16");
+  if (M == 0) return torch::empty({0, N}, x.options());
+  if (M <= 64 && K % 128 == 0) {
+    auto y = torch::empty({M, N}, x.options());
+    const int64_t ws_bytes = lvllm_skinny_gemm_w4a16_workspace_bytes((int)M, (int)N, (int)K);
+    torch::Tensor ws;
+    if (ws_bytes > 0) ws = torch::empty({ws_bytes / 4}, x.options().dtype(torch::kFloat));
+    const int rc = lvllm_skinny_gemm_w4a16(y.data_ptr(), x.data_ptr(), w4_packed.data_ptr(), meta.data_ptr(),
+                                           bias ? bias->data_ptr() : nullptr, (int)M, (int)N, (int)K, (int)group_size,
+                                           x.stride(0), dt, ws_bytes > 0 ? ws.data_ptr() : nullptr, ws_bytes,
+                                           current_stream(x));
+    if (rc == 0) return y;
+    TORCH_CHECK(rc == 3, lvllm_last_error());  // 3: strides / alignment outside the envelope -> the route below
+  }
+  auto wd = torch::empty({K, N}, x.options());
+  check(lvllm_awq_dequantize_packed(wd.data_ptr(), w4_packed.data_ptr(), meta.data_ptr(), (int)N, (int)K,
+                                    (int)group_size, dt, current_stream(x)));
+  auto y = at::matmul(x, wd);
+  if (bias) y.add_(*bias);
+  return y;
+}
+
+// The reference's operator on checkpoint tensors: repacks on every call, then streams -- correct, not fast; a host
+// that keeps its weights calls awq_pack once and skinny_linear_w4a16 per step.
+torch::Tensor awq_gemm(const torch::Tensor& in_feats, const torch::Tensor& qweight, const torch::Tensor& scales,
+                       const torch::Tensor& qzeros, int64_t split_k_iters) {
+  const AwqShape s = awq_shape(qweight, qzeros, scales, "awq_gemm");
+  TORCH_CHECK(in_feats.dim() >= 1 && in_feats.size(-1) == s.K && in_feats.scalar_type() == scales.scalar_type(),
+              "awq_gemm: in_feats [..., K] of the scales' dtype");
+  const auto x = in_feats.reshape({-1, s.K});
+  if (s.N % 16 != 0 || lvllm_awq_meta_bytes((int)s.N, (int)s.K, (int)s.G) == 0)  // no packed form: dequantise, multiply
+    return at::matmul(x, awq_dequantize(qweight, scales, qzeros, 0, 0, 0));
+  auto [w4, meta] = awq_pack(qweight, qzeros, scales);
+  return skinny_linear_w4a16(x, w4, meta, s.N, s.K, s.G, std::nullopt);
+}
+
 int64_t get_device_attribute(int64_t attribute, int64_t device_id) {
   return lvllm_get_device_attribute(attribute, device_id);
 }
@@ -1175,6 +1277,13 @@ TORCH_LIBRARY(_C, ops) {
       "                 Tensor! key, int head_size,"
       "                 Tensor cos_sin_cache, bool is_neox) -> ()");
   ops.impl("rotary_embedding", torch::kCUDA, &rotary_embedding);
+
+  // AWQ, torch_bindings.cpp:121-126 of the reference (schemas as inferred from gemm_kernels.cu:413-418,469-471)
+  ops.def("awq_gemm(Tensor _in_feats, Tensor _kernel, Tensor _scaling_factors, Tensor _zeros, int split_k_iters) -> Tensor");
+  ops.impl("awq_gemm", torch::kCUDA, &awq_gemm);
+  ops.def("awq_dequantize(Tensor _kernel, Tensor _scaling_factors, Tensor _zeros, int split_k_iters, int thx, int thy) "
+          "-> Tensor");
+  ops.impl("awq_dequantize", torch::kCUDA, &awq_dequantize);
 }
 
 TORCH_LIBRARY(_C_cache_ops, cache_ops) {
@@ -1219,6 +1328,12 @@ TORCH_LIBRARY(_C_amd, amd) {
   amd.impl("skinny_linear_packed", torch::kCUDA, &skinny_linear_packed);
   amd.def("pack_weight(Tensor w) -> Tensor");
   amd.impl("pack_weight", torch::kCUDA, &pack_weight);
+  // W4A16 (AWQ): repack once after loading, then stream the packed pair per step
+  amd.def("awq_pack(Tensor qweight, Tensor qzeros, Tensor scales) -> (Tensor, Tensor)");
+  amd.impl("awq_pack", torch::kCUDA, &awq_pack);
+  amd.def("skinny_linear_w4a16(Tensor x, Tensor w4_packed, Tensor meta, int N, int K, int group_size, "
+          "Tensor? bias) -> Tensor");
+  amd.impl("skinny_linear_w4a16", torch::kCUDA, &skinny_linear_w4a16);
   amd.def("gelu(Tensor! out, Tensor x) -> ()");
   amd.impl("gelu", torch::kCUDA, &gelu);
   amd.def("add_layer_norm(Tensor! out, Tensor x, Tensor? y, Tensor weight, Tensor bias, float epsilon) -> ()");

@@ -38,7 +38,10 @@ class ModelConfig:
     o_proj_partials_min_rows: int = 33
     # "fp8": W8A8 projections (BASELINE config 5): per-tensor e4m3 weights, static per-tensor
     # activation scales calibrated once on a random batch (the reference's activation_scheme="static")
+    # "awq": W4A16 projections (4-bit weights in groups of awq_group_size input channels, 16-bit activations); the
+    # lm_head stays 16-bit, as AWQ checkpoints keep it
     quantization: Optional[str] = None
+    awq_group_size: int = 128
     # W8A8 decode steps: activations quantised once by their producer (norm launches, SwiGLU epilogue) and handed to
     # the projections as fp8 (bit-identical to quantising inside every projection; off = A/B runs)
     fp8_activations_once: bool = True

@@ -22,7 +22,8 @@ class Weight:
     weight-streaming kernel reads one contiguous KiB per wave load (csrc/skinny_gemm.hip).
     Twice the bytes; sized for 288 GB of HBM."""
 
-    __slots__ = ("w", "packed", "N", "K", "w8_t", "w8_packed", "w_scale", "x_scale", "x_absmax")
+    __slots__ = ("w", "packed", "N", "K", "w8_t", "w8_packed", "w_scale", "x_scale", "x_absmax", "awq", "w4_packed",
+                 "w4_meta")
 
     def __init__(self, w: torch.Tensor, pack: bool = True):
         self.w = w
@@ -31,9 +32,32 @@ class Weight:
         self.packed = torch.ops._C_amd.pack_weight(w) if ok else None
         self.w8_t = self.w8_packed = self.w_scale = self.x_scale = None
         self.x_absmax = None  # calibration: running max |x| of this projection's input
+        self.awq = self.w4_packed = self.w4_meta = None  # W4A16: (qweight, qzeros, scales) and their packed pair
 
     def numel(self) -> int:
         return self.N * self.K
+
+    def nbytes(self) -> int:
+        """Bytes of one copy of the weight in the format it is held in (the packed twins hold the same again)."""
+        if self.awq is not None:
+            return sum(t.numel() * t.element_size() for t in self.awq)
+        return self.numel() * (1 if self.w8_t is not None else self.w.element_size())
+
+    @staticmethod
+    def awq_ok(N: int, K: int, group_size: int) -> bool:
+        """The envelope of the W4A16 streaming kernel (lvllm_skinny_gemm_w4a16)."""
+        return (group_size in (32, 64, 128) and N % 16 == 0 and K % 128 == 0
+                and (N // 16) * (K // 128) * 1024 < (1 << 32) - 16)
+
+    def quantize_awq(self, group_size: int) -> None:
+        """4-bit group-quantised weights (quantization/awq.py: plain round-to-nearest, no checkpoint is available):
+        the checkpoint-layout tensors stay for batches above 64 rows, their packed pair serves decode; the 16-bit
+        copies are dropped."""
+        from ..quantization import pack_awq_weight, quantize_awq
+        assert self.awq_ok(self.N, self.K, group_size), "outside the W4A16 kernel's envelope"
+        self.awq = quantize_awq(self.w, group_size)
+        self.w4_packed, self.w4_meta = pack_awq_weight(*self.awq)
+        self.w = self.packed = None
 
     def quantize_fp8(self) -> None:
         """Per-tensor e4m3 weights + the calibrated static activation scale; the 16-bit copies are
@@ -58,6 +82,9 @@ def linear(x: torch.Tensor, w: "Weight", bias: Optional[torch.Tensor] = None) ->
             return torch.ops._C_amd.skinny_linear_w8a8(x, w.w8_packed, w.w_scale, w.x_scale, w.N, w.K, bias)
         from ..quantization import apply_fp8_linear
         return apply_fp8_linear(x, w.w8_t, w.w_scale, input_scale=w.x_scale, bias=bias)
+    if w.w4_packed is not None:  # W4A16: the streaming kernel up to 64 rows, dequantise + library GEMM above
+        from ..quantization import apply_awq_linear
+        return apply_awq_linear(x, w.w4_packed, w.w4_meta, *w.awq, bias=bias)
     if _CALIBRATING:
         m = x.detach().abs().amax()
         w.x_absmax = m if w.x_absmax is None else torch.maximum(w.x_absmax, m)
@@ -124,10 +151,18 @@ class DecoderModel:
             attn_impl.fuse_rope_over_fp8_cache = cfg.rope_in_attention_fp8
         self.q_size = cfg.num_attention_heads * cfg.head_dim
         self.kv_size = cfg.num_key_value_heads * cfg.head_dim
-        if cfg.quantization is not None:
-            if cfg.quantization != "fp8":
-                raise ValueError(f"unsupported quantization {cfg.quantization!r}")
+        if cfg.quantization == "fp8":
             self._quantize_fp8(gen)
+        elif cfg.quantization == "awq":
+            # the four projections of every layer; the lm_head stays 16-bit (arg-max epilogue included), and so does
+            # a projection outside the kernel's envelope
+            for l in self.layers:
+                for w in (l.qkv, l.o, l.gate_up, l.down):
+                    if w.w.is_cuda and Weight.awq_ok(w.N, w.K, cfg.awq_group_size):
+                        w.quantize_awq(cfg.awq_group_size)
+            torch.cuda.empty_cache()
+        elif cfg.quantization is not None:
+            raise ValueError(f"unsupported quantization {cfg.quantization!r}")
 
     def all_weights(self) -> List["Weight"]:
         ws = [self.lm_head]
@@ -168,8 +203,7 @@ class DecoderModel:
         torch.cuda.empty_cache()
 
     def weight_bytes(self) -> int:
-        n = sum(w.numel() for w in self.all_weights())
-        return n * (1 if self.cfg.quantization == "fp8" else self.embed.element_size())
+        return sum(w.nbytes() for w in self.all_weights())  # what each weight really holds
 
     def _add_norm(self, x, residual: torch.Tensor, weight: torch.Tensor) -> torch.Tensor:
         """residual += x; return norm(residual) * weight.  `x` is either the projection output

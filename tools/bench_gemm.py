@@ -8,6 +8,80 @@ import light_vllm_amd  # noqa
 from light_vllm_amd import _custom_ops  # noqa
 
 dev = "cuda:0"
+
+
+def awq_leg(out_path):
+    """--awq [out.md]: the W4A16 launch against the bf16 packed launch of the same shape, same process, G = 128.
+    Weights rotate through > 1 GB of buffers per format (beyond L2 and the 256 MB last-level cache), 5 warm-up
+    launches, then REGIONS regions of PER launches each, the two formats alternating launch by launch inside a region;
+    a region's figure is the median of its device-event times, and every region is listed."""
+    REGIONS, PER, G = 5, 40, 128
+    shapes = [("qkv", 6144, 4096), ("o", 4096, 4096), ("gate_up", 28672, 4096), ("down", 4096, 14336)]
+    lines = ["| shape | M | W4A16 us (regions) | bf16 packed us (regions) | W4A16 graph us | bf16 graph us | W4 bytes | "
+             "W4 TB/s | bf16 TB/s | speed-up |", "|---|---|---|---|---|---|---|---|---|---|"]
+    for name, N, K in shapes:
+        qw = torch.randint(-2 ** 31, 2 ** 31, (K, N // 8), device=dev, dtype=torch.int64).to(torch.int32)
+        qz = torch.randint(-2 ** 31, 2 ** 31, (K // G, N // 8), device=dev, dtype=torch.int64).to(torch.int32)
+        sc = (torch.rand(K // G, N, device=dev) * 0.01 + 1e-3).to(torch.bfloat16)
+        w4, meta = torch.ops._C_amd.awq_pack(qw, qz, sc)
+        w16 = torch.ops._C_amd.pack_weight((torch.randn(N, K, device=dev) * 0.02).to(torch.bfloat16))
+        b4, b16 = w4.numel() * 4 + meta.numel() * 4, N * K * 2
+        n4, n16 = min(160, int(1.1e9 // b4) + 1), int(1.1e9 // b16) + 1
+        w4s, w16s = [(w4.clone(), meta.clone()) for _ in range(n4)], [w16.clone() for _ in range(n16)]
+        del qw, qz
+        for M in (1, 32, 64):
+            x = (torch.randn(M, K, device=dev) * 0.5).to(torch.bfloat16)
+            f4 = lambda i: torch.ops._C_amd.skinny_linear_w4a16(x, w4s[i % n4][0], w4s[i % n4][1], N, K, G, None)  # noqa: E731
+            f16 = lambda i: torch.ops._C_amd.skinny_linear_packed(x, w16s[i % n16], None, N, K)  # noqa: E731
+            for i in range(5):
+                f4(i); f16(i)
+            torch.cuda.synchronize()
+            r4, r16, it = [], [], 0
+            for _ in range(REGIONS):
+                evs = []
+                for _ in range(PER):
+                    e = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+                    e[0].record(); f4(it); e[1].record(); f16(it); e[2].record()
+                    evs.append(e); it += 1
+                torch.cuda.synchronize()
+                r4.append(sorted(e[0].elapsed_time(e[1]) * 1e3 for e in evs)[PER // 2])
+                r16.append(sorted(e[1].elapsed_time(e[2]) * 1e3 for e in evs)[PER // 2])
+            # the same launches without the host in the loop: one captured graph per format that walks every buffer
+            # once, replayed REGIONS times; us per launch = replay time / launches (min-max over the replays)
+            def replayed(fn, n):
+                graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(graph):
+                    for i in range(n):
+                        fn(i)
+                graph.replay()
+                torch.cuda.synchronize()
+                ts = []
+                for _ in range(REGIONS):
+                    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    a.record(); graph.replay(); b.record()
+                    torch.cuda.synchronize()
+                    ts.append(a.elapsed_time(b) * 1e3 / n)
+                return ts
+            g4, g16 = replayed(f4, n4), replayed(f16, n16)
+            xy = M * K * 2 + M * N * 2
+            m4, m16 = sorted(r4)[REGIONS // 2], sorted(r16)[REGIONS // 2]
+            fmt = lambda r: " ".join(f"{t:.1f}" for t in r)  # noqa: E731
+            verdict = "faster beyond the spread" if max(r4) < min(r16) else "NOT faster beyond the spread"
+            lines.append(f"| {name} {N}x{K} | {M} | {m4:.1f} ({fmt(r4)}) | {m16:.1f} ({fmt(r16)}) | "
+                         f"{min(g4):.1f}-{max(g4):.1f} | {min(g16):.1f}-{max(g16):.1f} | {b4 + xy} | "
+                         f"{(b4 + xy) / m4 / 1e6:.2f} | {(b16 + xy) / m16 / 1e6:.2f} | {m16 / m4:.2f}x, {verdict} |")
+            print(lines[-1], flush=True)
+        del w4s, w16s
+        torch.cuda.empty_cache()
+    if out_path:
+        with open(out_path, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if len(sys.argv) > 1 and sys.argv[1] == "--awq":
+    awq_leg(sys.argv[2] if len(sys.argv) > 2 else None)
+    sys.exit(0)
+
 M = int(sys.argv[1]) if len(sys.argv) > 1 else 32
 for name, N, K in [("qkv", 6144, 4096), ("o", 4096, 4096), ("gate_up", 28672, 4096), ("down", 4096, 14336), ("lm_head", 128256, 4096)]:
     nw = max(2, min(12, int(1.2e9 // (N * K * 2))))
