@@ -577,6 +577,28 @@ int lvllm_skinny_gemm_w4a16(void* y, const void* x, const void* w4_packed, const
                             int N, int K, int group_size, int64_t ldx, int dtype, void* workspace,
                             int64_t workspace_bytes, void* stream);
 
+/* ---- W8A8 int8: per-token x per-channel scales (csrc/int8_quant.hip, csrc/int8_gemm.hip) ----------------------
+ * The compressed-tensors / SmoothQuant scheme of the reference (w8a8_utils.py:192-209, int8_quant_kernels.cu,
+ * scaled_mm_c2x.cuh:117-129).  input [num_tokens, hidden_size] contiguous f16 / bf16 / f32, out int8 of that shape.
+ * lvllm_static_scaled_int8_quant:  q = sat_i8(rint(float(x) / *scale)), IEEE division, halves to even.
+ * lvllm_dynamic_scaled_int8_quant: per row a = max |x|, scales[row] = a / 127.0f, q = sat_i8(rint(float(x) *
+ * (127.0f / a))); an all-zero row gives scale 0 and zeros (the reference gives NaN there).
+ * lvllm_skinny_gemm_w8a8_int8: y [M, N] = T(x_scale[m] * (w_scale[n] * float(acc)) + bias[n]), acc = x_q . Wq^T in
+ * int32 (exact: the result does not depend on how K is split), two fp32 products in that order and a separate add;
+ * x_q int8 [M <= 64, K] (rows ldx BYTES apart, ldx % 16 == 0), w_packed = int8 weights [N, K] packed by
+ * lvllm_pack_weight on their [N, K/2] 16-bit view, x_scale fp32 [M], w_scale fp32 [N] (16-byte aligned), bias [N] of
+ * T or null, T = bf16 / f16.  N % 16 == 0, K % 64 == 0, K < 131072; returns 3 and launches nothing outside the
+ * envelope.  workspace: int32 split-K partials, lvllm_skinny_gemm_w8a8_int8_workspace_bytes(M, N, K) bytes (0 when K
+ * fits one workgroup), 16-byte aligned. */
+int lvllm_static_scaled_int8_quant(void* out, const void* input, const float* scale, int64_t num_tokens,
+                                   int hidden_size, int dtype, void* stream);
+int lvllm_dynamic_scaled_int8_quant(void* out, float* scales, const void* input, int64_t num_tokens, int hidden_size,
+                                    int dtype, void* stream);
+int64_t lvllm_skinny_gemm_w8a8_int8_workspace_bytes(int M, int N, int K);
+int lvllm_skinny_gemm_w8a8_int8(void* y, const void* x_q, const void* w_packed, const float* x_scale,
+                                const float* w_scale, const void* bias, int M, int N, int K, int64_t ldx, int dtype,
+                                void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- device queries (csrc/cuda_utils.h, torch_bindings.cpp:271-279) ------- */
 int64_t lvllm_get_device_attribute(int64_t attribute, int64_t device_id);
 int64_t lvllm_get_max_shared_memory_per_block_device_attribute(int64_t device_id);

@@ -8,7 +8,7 @@ light-vllm_amd/csrc/torch_bindings.cpp registers with the reference's schema and
 that runs a hand-written gfx950 kernel.  Importing this module loads the native
 libraries and raises if they are missing -- there is no other implementation.
 """
-from typing import List, Optional
+from typing import List, Optional, Tuple
 
 import torch
 
@@ -124,6 +124,29 @@ def scaled_fp8_quant(input: torch.Tensor, scale: Optional[torch.Tensor] = None,
         assert scale.numel() == 1 or num_token_padding is None
         _C.static_scaled_fp8_quant(output, input, scale)
     return output, scale
+
+
+def scaled_int8_quant(input: torch.Tensor, scale: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """int8 activations (_custom_ops.py:369-395 of the reference): with `scale` static per-tensor quantisation,
+    q = sat(rint(x / scale)); without, dynamic per-token: scale = max|x| / 127 per row, returned as [tokens, 1] fp32.
+    An all-zero row gives scale 0 and zeros."""
+    output = torch.empty_like(input, dtype=torch.int8)
+    if scale is not None:
+        _C.static_scaled_int8_quant(output, input, scale)
+        return output, scale
+    input_scales = torch.empty((input.numel() // input.shape[-1], 1), device=input.device, dtype=torch.float32)
+    _C.dynamic_scaled_int8_quant(output, input, input_scales)
+    return output, input_scales
+
+
+def cutlass_scaled_mm(a: torch.Tensor, b: torch.Tensor, scale_a: torch.Tensor, scale_b: torch.Tensor,
+                      out_dtype: torch.dtype, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out = scale_a[m] * (scale_b[n] * (a . b)) + bias for int8 a [M, K] and b [K, N] (column-major, weight.t()),
+    int32 accumulation -- the reference's operator name, served by this package's HIP kernel; fp8 operands are
+    refused (quantization.apply_fp8_linear is their route)."""
+    out = torch.empty((a.shape[0], b.shape[1]), dtype=out_dtype, device=a.device)
+    _C.cutlass_scaled_mm(out, a, b, scale_a, scale_b, bias)
+    return out
 
 
 def awq_dequantize(qweight: torch.Tensor, scales: torch.Tensor, zeros: torch.Tensor, split_k_iters: int,

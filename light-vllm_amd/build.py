@@ -32,9 +32,11 @@ HIP_SOURCES = [
     "attention_f16.hip",
     "skinny_gemm.hip",
     "awq_gemm.hip",
+    "int8_gemm.hip",
     "prefill_attention.hip",
     "prepare_inputs.hip",
     "fp8_quant.hip",
+    "int8_quant.hip",
     "sampler.hip",
 ]
 

@@ -1210,6 +1210,141 @@ torch::Tensor awq_gemm(const torch::Tensor& in_feats, const torch::Tensor& qweig
   return skinny_linear_w4a16(x, w4, meta, s.N, s.K, s.G, std::nullopt);
 }
 
+// ---- W8A8 int8 (compressed-tensors): int8_quant_kernels.cu, scaled_mm_c2x.cuh:117-129,164, w8a8_utils.py:192-209 of
+// the reference.  All-zero rows of dynamic_scaled_int8_quant give scale 0 and zeros here (NaN in the reference).
+struct Int8QuantShape { int64_t tokens, hidden; };
+Int8QuantShape check_int8_quant(const torch::Tensor& out, const torch::Tensor& input, const char* op) {
+  LV_CHECK_DEVICE(input);
+  LV_CHECK_DEVICE(out);
+  TORCH_CHECK(out.scalar_type() == at::kChar && out.sizes() == input.sizes(), op, ": out must be int8 of input's shape");
+  TORCH_CHECK(input.dim() >= 1 && input.is_contiguous() && out.is_contiguous(), op, ": input / out must be contiguous");
+  const int64_t hidden = input.size(-1);
+  TORCH_CHECK(hidden > 0 && hidden < ((int64_t)1 << 31), op, ": hidden size out of range");
+  return {input.numel() / hidden, hidden};
+}
+
+void static_scaled_int8_quant(torch::Tensor& out, torch::Tensor const& input, torch::Tensor const& scale) {
+  const Int8QuantShape s = check_int8_quant(out, input, "static_scaled_int8_quant");
+  TORCH_CHECK(scale.scalar_type() == at::kFloat && scale.is_cuda() && scale.numel() == 1,
+              "static_scaled_int8_quant: scale must be one fp32 value on the GPU");
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(device_of(input));
+  check(lvllm_static_scaled_int8_quant(out.data_ptr(), input.data_ptr(), scale.data_ptr<float>(), s.tokens,
+                                       (int)s.hidden, dtype_code(input, "static_scaled_int8_quant"),
+                                       current_stream(input)));
+}
+
+void dynamic_scaled_int8_quant(torch::Tensor& out, torch::Tensor const& input, torch::Tensor& scale) {
+  const Int8QuantShape s = check_int8_quant(out, input, "dynamic_scaled_int8_quant");
+  TORCH_CHECK(scale.scalar_type() == at::kFloat && scale.is_cuda() && scale.is_contiguous() && scale.numel() == s.tokens,
+              "dynamic_scaled_int8_quant: scale must be contiguous fp32 with one element per token");
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(device_of(input));
+  check(lvllm_dynamic_scaled_int8_quant(out.data_ptr(), scale.data_ptr<float>(), input.data_ptr(), s.tokens,
+                                        (int)s.hidden, dtype_code(input, "dynamic_scaled_int8_quant"),
+                                        current_stream(input)));
+}
+
+// [N, K] int8 row-major -> the streaming order: lvllm_pack_weight on the [N, K/2] 16-bit view of the same bytes
+torch::Tensor int8_pack(const torch::Tensor& w_q) {
+  TORCH_CHECK(w_q.is_cuda() && w_q.dim() == 2 && w_q.is_contiguous() && w_q.scalar_type() == at::kChar,
+              "int8_pack: contiguous [N, K] int8 GPU tensor");
+  TORCH_CHECK(w_q.size(0) > 0 && w_q.size(0) % 16 == 0 && w_q.size(1) > 0 && w_q.size(1) % 64 == 0,
+              "int8_pack: N % 16 == 0 and K % 64 == 0");
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(device_of(w_q));
+  auto out = torch::empty_like(w_q);
+  check(lvllm_pack_weight(out.data_ptr(), w_q.data_ptr(), (int)w_q.size(0), (int)(w_q.size(1) / 2), LVLLM_F16,
+                          current_stream(w_q)));
+  return out;
+}
+
+// a scale of one element or of `n`: fp32 [n] on the device
+torch::Tensor int8_scale_vector(const torch::Tensor& s, int64_t n, const char* what) {
+  TORCH_CHECK(s.is_cuda() && s.scalar_type() == at::kFloat && (s.numel() == 1 || s.numel() == n), what,
+              " must be fp32 on the GPU with one element or one per row / channel");
+  return s.numel() == n ? s.reshape({n}).contiguous() : s.reshape({1}).expand({n}).contiguous();
+}
+
+// y [M, N] (contiguous, bf16 / f16) = sx[m] * (sw[n] * (x_q . Wq^T)[m, n]) (+ bias) from the packed weight.  Above 64
+// rows the same kernel runs over chunks of 64 rows: exact, hence equal row for row to the <= 64 path, but the weights
+// stream once per chunk -- a correctness path.
+void int8_linear_into(torch::Tensor& y, const torch::Tensor& x_q_in, const torch::Tensor& w_packed,
+                      const torch::Tensor& x_scale, const torch::Tensor& w_scale, int64_t N, int64_t K,
+                      const std::optional<torch::Tensor>& bias, const char* op) {
+  LV_CHECK_DEVICE(x_q_in);
+  LV_CHECK_DEVICE(w_packed);
+  TORCH_CHECK(x_q_in.dim() == 2 && x_q_in.size(1) == K && x_q_in.scalar_type() == at::kChar, op, ": x_q must be [M, K] int8");
+  TORCH_CHECK(N > 0 && K > 0 && N % 16 == 0 && K % 64 == 0 && K < 131072, op, ": N % 16 == 0, K % 64 == 0, K < 131072");
+  TORCH_CHECK(w_packed.is_contiguous() && w_packed.element_size() == 1 && w_packed.numel() == N * K, op,
+              ": w_packed does not have the size int8_pack gives for this N, K");
+  TORCH_CHECK(y.scalar_type() == at::kHalf || y.scalar_type() == at::kBFloat16, op, ": the output is f16 or bf16");
+  TORCH_CHECK(!bias || (bias->is_cuda() && bias->is_contiguous() && bias->numel() == N &&
+                        bias->scalar_type() == y.scalar_type()),
+              op, ": bias must be [N] of the output's dtype");
+  const int64_t M = x_q_in.size(0);
+  if (M == 0) return;
+  const auto sx = int8_scale_vector(x_scale, M, "x_scale"), sw = int8_scale_vector(w_scale, N, "w_scale");
+  const bool strided_ok = x_q_in.stride(1) == 1 && x_q_in.stride(0) >= K && x_q_in.stride(0) % 16 == 0 &&
+                          ((uintptr_t)x_q_in.data_ptr() & 15) == 0;
+  const torch::Tensor x_q = strided_ok ? x_q_in : x_q_in.contiguous();
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(device_of(x_q));
+  const int64_t ws_bytes = lvllm_skinny_gemm_w8a8_int8_workspace_bytes((int)std::min<int64_t>(M, 64), (int)N, (int)K);
+  torch::Tensor ws;
+  if (ws_bytes > 0) ws = torch::empty({ws_bytes / 4}, x_q.options().dtype(torch::kInt));
+  const int dt = y.scalar_type() == at::kBFloat16 ? LVLLM_BF16 : LVLLM_F16;
+  for (int64_t m0 = 0; m0 < M; m0 += 64) {
+    const int64_t rows = std::min<int64_t>(64, M - m0);
+    check(lvllm_skinny_gemm_w8a8_int8((char*)y.data_ptr() + m0 * N * 2, (const char*)x_q.data_ptr() + m0 * x_q.stride(0),
+                                      w_packed.data_ptr(), sx.data_ptr<float>() + m0, sw.data_ptr<float>(),
+                                      bias ? bias->data_ptr() : nullptr, (int)rows, (int)N, (int)K, x_q.stride(0), dt,
+                                      ws_bytes > 0 ? ws.data_ptr() : nullptr, ws_bytes, current_stream(x_q)));
+  }
+}
+
+torch::Tensor skinny_linear_w8a8_int8(const torch::Tensor& x_q, const torch::Tensor& w_packed,
+                                      const torch::Tensor& x_scale, const torch::Tensor& w_scale, int64_t N, int64_t K,
+                                      const std::optional<torch::Tensor>& bias, at::ScalarType out_dtype) {
+  LV_CHECK_DEVICE(x_q);
+  TORCH_CHECK(x_q.dim() == 2, "skinny_linear_w8a8_int8: x_q must be [M, K] int8");
+  auto y = torch::empty({x_q.size(0), N}, x_q.options().dtype(out_dtype));
+  int8_linear_into(y, x_q, w_packed, x_scale, w_scale, N, K, bias, "skinny_linear_w8a8_int8");
+  return y;
+}
+
+// The reference's operator for int8 operands: a [M, K] row-major, b [K, N] with strides (1, K) (weight.t()), fp32
+// a_scales (1 or M) and b_scales (1 or N).  Inside the kernel's envelope b is packed on every call -- correct, not
+// fast; a host that keeps its weights calls int8_pack once and skinny_linear_w8a8_int8 per step.  Outside it (K % 64
+// or N % 16) the accumulators come from a float64 matmul of the integer operands, which is exact, and the same
+// epilogue is applied in fp32.
+void cutlass_scaled_mm(torch::Tensor& out, const torch::Tensor& a, const torch::Tensor& b, const torch::Tensor& a_scales,
+                       const torch::Tensor& b_scales, const std::optional<torch::Tensor>& bias) {
+  LV_CHECK_DEVICE(a);
+  LV_CHECK_DEVICE(b);
+  LV_CHECK_DEVICE(out);
+  TORCH_CHECK(a.scalar_type() == at::kChar && b.scalar_type() == at::kChar,
+              "cutlass_scaled_mm: only int8 a / b are served here (fp8 goes through apply_fp8_linear)");
+  TORCH_CHECK(a.dim() == 2 && b.dim() == 2 && out.dim() == 2 && a.size(1) == b.size(0) && out.size(0) == a.size(0) &&
+                  out.size(1) == b.size(1),
+              "cutlass_scaled_mm: a [M, K], b [K, N], out [M, N]");
+  const int64_t M = a.size(0), K = a.size(1), N = b.size(1);
+  TORCH_CHECK(a.stride(1) == 1 && b.stride(0) == 1 && (b.stride(1) == K || N == 1) && out.is_contiguous(),
+              "cutlass_scaled_mm: a row-major, b column-major (strides (1, K)), out contiguous");
+  TORCH_CHECK(out.scalar_type() == at::kHalf || out.scalar_type() == at::kBFloat16,
+              "cutlass_scaled_mm: out must be f16 or bf16");
+  TORCH_CHECK(!bias || (bias->is_cuda() && bias->numel() == N && bias->scalar_type() == out.scalar_type()),
+              "cutlass_scaled_mm: bias must be [N] of out's dtype");
+  if (M == 0 || N == 0) return;
+  const auto w_q = b.t();  // [N, K]
+  if (K > 0 && K % 64 == 0 && N % 16 == 0 && K < 131072) {
+    int8_linear_into(out, a, int8_pack(w_q.contiguous()), a_scales, b_scales, N, K,
+                     bias ? std::optional<torch::Tensor>(bias->contiguous()) : std::nullopt, "cutlass_scaled_mm");
+    return;
+  }
+  const auto sx = int8_scale_vector(a_scales, M, "a_scales"), sw = int8_scale_vector(b_scales, N, "b_scales");
+  const auto acc = at::matmul(a.to(at::kDouble), b.to(at::kDouble)).to(at::kFloat);  // exact integers, then RNE
+  auto r = sx.unsqueeze(1) * (sw.unsqueeze(0) * acc);
+  if (bias) r = r + bias->to(at::kFloat).unsqueeze(0);
+  out.copy_(r);
+}
+
 int64_t get_device_attribute(int64_t attribute, int64_t device_id) {
   return lvllm_get_device_attribute(attribute, device_id);
 }
@@ -1284,6 +1419,14 @@ TORCH_LIBRARY(_C, ops) {
   ops.def("awq_dequantize(Tensor _kernel, Tensor _scaling_factors, Tensor _zeros, int split_k_iters, int thx, int thy) "
           "-> Tensor");
   ops.impl("awq_dequantize", torch::kCUDA, &awq_dequantize);
+
+  // W8A8 int8, torch_bindings.cpp:159-162,215-224 of the reference
+  ops.def("static_scaled_int8_quant(Tensor! out, Tensor input, Tensor scale) -> ()");
+  ops.impl("static_scaled_int8_quant", torch::kCUDA, &static_scaled_int8_quant);
+  ops.def("dynamic_scaled_int8_quant(Tensor! out, Tensor input, Tensor! scale) -> ()");
+  ops.impl("dynamic_scaled_int8_quant", torch::kCUDA, &dynamic_scaled_int8_quant);
+  ops.def("cutlass_scaled_mm(Tensor! out, Tensor a, Tensor b, Tensor a_scales, Tensor b_scales, Tensor? bias) -> ()");
+  ops.impl("cutlass_scaled_mm", torch::kCUDA, &cutlass_scaled_mm);
 }
 
 TORCH_LIBRARY(_C_cache_ops, cache_ops) {
@@ -1334,6 +1477,12 @@ TORCH_LIBRARY(_C_amd, amd) {
   amd.def("skinny_linear_w4a16(Tensor x, Tensor w4_packed, Tensor meta, int N, int K, int group_size, "
           "Tensor? bias) -> Tensor");
   amd.impl("skinny_linear_w4a16", torch::kCUDA, &skinny_linear_w4a16);
+  // W8A8 int8: pack once after loading, then stream the packed weight per step with pre-quantised activations
+  amd.def("int8_pack(Tensor w_q) -> Tensor");
+  amd.impl("int8_pack", torch::kCUDA, &int8_pack);
+  amd.def("skinny_linear_w8a8_int8(Tensor x_q, Tensor w_packed, Tensor x_scale, Tensor w_scale, int N, int K, "
+          "Tensor? bias, ScalarType out_dtype) -> Tensor");
+  amd.impl("skinny_linear_w8a8_int8", torch::kCUDA, &skinny_linear_w8a8_int8);
   amd.def("gelu(Tensor! out, Tensor x) -> ()");
   amd.impl("gelu", torch::kCUDA, &gelu);
   amd.def("add_layer_norm(Tensor! out, Tensor x, Tensor? y, Tensor weight, Tensor bias, float epsilon) -> ()");

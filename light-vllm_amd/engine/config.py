@@ -40,6 +40,8 @@ class ModelConfig:
     # activation scales calibrated once on a random batch (the reference's activation_scheme="static")
     # "awq": W4A16 projections (4-bit weights in groups of awq_group_size input channels, 16-bit activations); the
     # lm_head stays 16-bit, as AWQ checkpoints keep it
+    # "int8": W8A8 int8 projections (per-channel weight scales, dynamic per-token activation scales, int32
+    # accumulation); the lm_head stays 16-bit
     quantization: Optional[str] = None
     awq_group_size: int = 128
     # W8A8 decode steps: activations quantised once by their producer (norm launches, SwiGLU epilogue) and handed to

@@ -23,7 +23,7 @@ class Weight:
     Twice the bytes; sized for 288 GB of HBM."""
 
     __slots__ = ("w", "packed", "N", "K", "w8_t", "w8_packed", "w_scale", "x_scale", "x_absmax", "awq", "w4_packed",
-                 "w4_meta")
+                 "w4_meta", "i8", "i8_packed", "i8_scale")
 
     def __init__(self, w: torch.Tensor, pack: bool = True):
         self.w = w
@@ -33,6 +33,7 @@ class Weight:
         self.w8_t = self.w8_packed = self.w_scale = self.x_scale = None
         self.x_absmax = None  # calibration: running max |x| of this projection's input
         self.awq = self.w4_packed = self.w4_meta = None  # W4A16: (qweight, qzeros, scales) and their packed pair
+        self.i8 = self.i8_packed = self.i8_scale = None  # W8A8 int8: row-major OR packed weight, per-channel scales
 
     def numel(self) -> int:
         return self.N * self.K
@@ -41,6 +42,8 @@ class Weight:
         """Bytes of one copy of the weight in the format it is held in (the packed twins hold the same again)."""
         if self.awq is not None:
             return sum(t.numel() * t.element_size() for t in self.awq)
+        if self.i8_scale is not None:
+            return self.numel() + self.i8_scale.numel() * self.i8_scale.element_size()
         return self.numel() * (1 if self.w8_t is not None else self.w.element_size())
 
     @staticmethod
@@ -57,6 +60,23 @@ class Weight:
         assert self.awq_ok(self.N, self.K, group_size), "outside the W4A16 kernel's envelope"
         self.awq = quantize_awq(self.w, group_size)
         self.w4_packed, self.w4_meta = pack_awq_weight(*self.awq)
+        self.w = self.packed = None
+
+    @staticmethod
+    def int8_ok(N: int, K: int) -> bool:
+        """The envelope of the W8A8 int8 streaming kernel (lvllm_skinny_gemm_w8a8_int8)."""
+        return N % 16 == 0 and K % 64 == 0 and K < 131072 and N * K < (1 << 32) - 16
+
+    def quantize_int8(self) -> None:
+        """int8 weights with one fp32 scale per output channel (quantization/int8.py); the 16-bit copies are dropped.
+        Inside the kernel's envelope only the packed form is kept, otherwise the row-major int8 weight for the exact
+        fallback of cutlass_scaled_mm."""
+        from ..quantization import pack_int8_weight, quantize_int8_weight
+        q, self.i8_scale = quantize_int8_weight(self.w)
+        if self.int8_ok(self.N, self.K):
+            self.i8_packed = pack_int8_weight(q)
+        else:
+            self.i8 = q
         self.w = self.packed = None
 
     def quantize_fp8(self) -> None:
@@ -85,6 +105,9 @@ def linear(x: torch.Tensor, w: "Weight", bias: Optional[torch.Tensor] = None) ->
     if w.w4_packed is not None:  # W4A16: the streaming kernel up to 64 rows, dequantise + library GEMM above
         from ..quantization import apply_awq_linear
         return apply_awq_linear(x, w.w4_packed, w.w4_meta, *w.awq, bias=bias)
+    if w.i8_scale is not None:  # W8A8 int8: dynamic per-token activation scales, then the int32 streaming kernel
+        from ..quantization import apply_int8_linear
+        return apply_int8_linear(x, w.i8_packed if w.i8_packed is not None else w.i8.t(), w.i8_scale, bias=bias)
     if _CALIBRATING:
         m = x.detach().abs().amax()
         w.x_absmax = m if w.x_absmax is None else torch.maximum(w.x_absmax, m)
@@ -160,6 +183,14 @@ class DecoderModel:
                 for w in (l.qkv, l.o, l.gate_up, l.down):
                     if w.w.is_cuda and Weight.awq_ok(w.N, w.K, cfg.awq_group_size):
                         w.quantize_awq(cfg.awq_group_size)
+            torch.cuda.empty_cache()
+        elif cfg.quantization == "int8":
+            # the four projections of every layer; activations are quantised per token in front of each of them
+            # (dynamic_scaled_int8_quant), the lm_head stays 16-bit
+            for l in self.layers:
+                for w in (l.qkv, l.o, l.gate_up, l.down):
+                    if w.w.is_cuda:
+                        w.quantize_int8()
             torch.cuda.empty_cache()
         elif cfg.quantization is not None:
             raise ValueError(f"unsupported quantization {cfg.quantization!r}")

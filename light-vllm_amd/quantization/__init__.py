@@ -2,7 +2,9 @@
 quantisation by this package's HIP kernels, GEMM + dequantisation through `torch._scaled_mm`
 (hipBLASLt fp8 MFMA on gfx950, OCP e4m3fn) -- the reference's own route on ROCm, where its CUTLASS
 kernels do not exist.  AWQ W4A16 (backends/quantization/awq.py): load-time repack and the gfx950
-weight-streaming kernel with in-register dequantisation."""
+weight-streaming kernel with in-register dequantisation.  W8A8 int8 (w8a8_utils.py:192-209): per-token activation
+quantisation and the int32-accumulating weight-streaming kernel, where the reference calls CUTLASS."""
 from .awq import AWQConfig, apply_awq_linear, pack_awq_weight, quantize_awq  # noqa: F401
 from .fp8 import (apply_fp8_linear, pack_fp8_weight, per_tensor_quantize_weight,  # noqa: F401
                   skinny_fp8_linear)
+from .int8 import apply_int8_linear, pack_int8_weight, quantize_int8_weight  # noqa: F401

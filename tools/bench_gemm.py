@@ -78,6 +78,106 @@ def awq_leg(out_path):
             f.write("\n".join(lines) + "\n")
 
 
+def int8_leg(out_path):
+    """--int8 [out.md]: the W8A8 int8 launch (pre-quantised activations, per-token x per-channel scales) against the
+    fp8 launch on pre-quantised activations (skinny_linear_w8a8_q: the same bytes per weight; it serves <= 32 rows, the
+    M = 64 column stays empty) and the bf16 packed launch, same process.  Weights rotate through > 1 GB of buffers per
+    format, 5 warm-up launches, then REGIONS regions of PER launches each, the formats alternating launch by launch
+    inside a region; a region's figure is the median of its device-event times, and every region is listed.  Then the
+    activation quantisation kernels alone, 32 rows of bf16 at H = 4096 and 14336."""
+    import os
+    REGIONS, PER = 5, 40
+    shapes = [("qkv", 6144, 4096), ("o", 4096, 4096), ("gate_up", 28672, 4096), ("down", 4096, 14336)]
+    fmt = lambda r: " ".join(f"{t:.1f}" for t in r)  # noqa: E731
+    med = lambda r: sorted(r)[len(r) // 2]  # noqa: E731
+    lines = [f"LVLLM_I8_STEPS={os.environ.get('LVLLM_I8_STEPS', '8')} "
+             f"LVLLM_I8_INFLIGHT={os.environ.get('LVLLM_I8_INFLIGHT', '8')}", "",
+             "| shape | M | int8 us (regions) | fp8 q us (regions) | bf16 packed us (regions) | int8 TB/s | fp8 TB/s | "
+             "bf16 TB/s | int8 vs fp8 |", "|---|---|---|---|---|---|---|---|---|"]
+    one = torch.ones(1, device=dev)
+    for name, N, K in shapes:
+        w8 = torch.ops._C_amd.int8_pack(torch.randint(-128, 128, (N, K), device=dev, dtype=torch.int8))
+        w16 = torch.ops._C_amd.pack_weight((torch.randn(N, K, device=dev) * 0.02).to(torch.bfloat16))
+        sw = torch.rand(N, device=dev) * 1e-3 + 1e-4
+        n8, n16 = int(1.1e9 // (N * K)) + 1, int(1.1e9 // (N * K * 2)) + 1
+        w8s, w16s = [w8.clone() for _ in range(n8)], [w16.clone() for _ in range(n16)]
+        wf8s = [w.view(torch.uint8) for w in w8s]  # the fp8 launch streams the same buffers: any byte is an fp8 value
+        for M in (1, 32, 64):
+            xq = torch.randint(-128, 128, (M, K), device=dev, dtype=torch.int8)
+            x8 = torch.randint(0, 120, (M, K), device=dev, dtype=torch.uint8).view(torch.float8_e4m3fn)  # finite values
+            x16 = (torch.randn(M, K, device=dev) * 0.5).to(torch.bfloat16)
+            sx = torch.rand(M, device=dev) * 1e-2 + 1e-3
+            fs = [lambda i: torch.ops._C_amd.skinny_linear_w8a8_int8(xq, w8s[i % n8], sx, sw, N, K, None, torch.bfloat16)]
+            if M <= 32:
+                fs.append(lambda i: torch.ops._C_amd.skinny_linear_w8a8_q(x8, wf8s[i % n8], one, one, N, K, None,
+                                                                          torch.bfloat16))
+            fs.append(lambda i: torch.ops._C_amd.skinny_linear_packed(x16, w16s[i % n16], None, N, K))
+            for i in range(5):
+                for f in fs:
+                    f(i)
+            torch.cuda.synchronize()
+            regions, it = [[] for _ in fs], 0
+            for _ in range(REGIONS):
+                evs = []
+                for _ in range(PER):
+                    e = [torch.cuda.Event(enable_timing=True) for _ in range(len(fs) + 1)]
+                    e[0].record()
+                    for j, f in enumerate(fs):
+                        f(it)
+                        e[j + 1].record()
+                    evs.append(e)
+                    it += 1
+                torch.cuda.synchronize()
+                for j in range(len(fs)):
+                    regions[j].append(med([e[j].elapsed_time(e[j + 1]) * 1e3 for e in evs]))
+            r8, r16 = regions[0], regions[-1]
+            rf = regions[1] if M <= 32 else None
+            b8 = N * K + M * K + M * N * 2 + 4 * (M + N)
+            b16 = N * K * 2 + M * K * 2 + M * N * 2
+            if rf is None:
+                verdict = ""
+            elif min(r8) > max(rf):
+                verdict = f"{med(r8) / med(rf):.2f}x the time, SLOWER beyond the spread"
+            elif max(r8) < min(rf):
+                verdict = f"{med(r8) / med(rf):.2f}x the time, faster beyond the spread"
+            else:
+                verdict = f"{med(r8) / med(rf):.2f}x the time, within the spread"
+            lines.append(f"| {name} {N}x{K} | {M} | {med(r8):.1f} ({fmt(r8)}) | "
+                         + (f"{med(rf):.1f} ({fmt(rf)})" if rf else "") + f" | {med(r16):.1f} ({fmt(r16)}) | "
+                         f"{b8 / med(r8) / 1e6:.2f} | " + (f"{b8 / med(rf) / 1e6:.2f}" if rf else "") +
+                         f" | {b16 / med(r16) / 1e6:.2f} | {verdict} |")
+            print(lines[-1], flush=True)
+        del w8s, w16s, wf8s
+        torch.cuda.empty_cache()
+    lines += ["", "| quantisation, 32 rows of bf16 | H | us per call (regions) |", "|---|---|---|"]
+    for H in (4096, 14336):
+        x = (torch.randn(32, H, device=dev) * 0.5).to(torch.bfloat16)
+        q, sd, st = torch.empty(32, H, device=dev, dtype=torch.int8), torch.empty(32, 1, device=dev), one * 0.05
+        for label, f in (("dynamic_scaled_int8_quant", lambda: torch.ops._C.dynamic_scaled_int8_quant(q, x, sd)),
+                         ("static_scaled_int8_quant", lambda: torch.ops._C.static_scaled_int8_quant(q, x, st))):
+            for _ in range(5):
+                f()
+            torch.cuda.synchronize()
+            rs = []
+            for _ in range(REGIONS):
+                evs = []
+                for _ in range(PER):
+                    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    a.record(); f(); b.record()
+                    evs.append((a, b))
+                torch.cuda.synchronize()
+                rs.append(med([a.elapsed_time(b) * 1e3 for a, b in evs]))
+            lines.append(f"| {label} | {H} | {med(rs):.1f} ({fmt(rs)}) |")
+            print(lines[-1], flush=True)
+    if out_path:
+        with open(out_path, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if len(sys.argv) > 1 and sys.argv[1] == "--int8":
+    int8_leg(sys.argv[2] if len(sys.argv) > 2 else None)
+    sys.exit(0)
+
 if len(sys.argv) > 1 and sys.argv[1] == "--awq":
     awq_leg(sys.argv[2] if len(sys.argv) > 2 else None)
     sys.exit(0)
