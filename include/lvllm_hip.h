@@ -65,7 +65,9 @@ const char* lvllm_version(void);
  * longest chunk has at least this many query tokens take the 32x32-MFMA body, and so do launches with chunks of 16+
  * tokens whose grid fits the CUs at once; 0 = never), "varlen_dense" (1 | 0: lvllm_varlen_attention's long plain
  * launches read key/value in place instead of packing them first), "varlen_dense_waves" (waves per workgroup of that
- * launch: 8, 4, or 0 = by the longest sequence).  lvllm_get_tuning reads a knob back. */
+ * launch: 8, 4, or 0 = by the longest sequence), "int8_tiled_min_rows" (the torch layer's W8A8 int8 linear: row count
+ * from which the LDS-tiled kernel runs instead of 64-row chunks of the streaming one).  lvllm_get_tuning reads a knob
+ * back. */
 int lvllm_set_tuning(const char* key, int value);
 int lvllm_get_tuning(const char* key, int* value);
 
@@ -589,7 +591,14 @@ int lvllm_skinny_gemm_w4a16(void* y, const void* x, const void* w4_packed, const
  * lvllm_pack_weight on their [N, K/2] 16-bit view, x_scale fp32 [M], w_scale fp32 [N] (16-byte aligned), bias [N] of
  * T or null, T = bf16 / f16.  N % 16 == 0, K % 64 == 0, K < 131072; returns 3 and launches nothing outside the
  * envelope.  workspace: int32 split-K partials, lvllm_skinny_gemm_w8a8_int8_workspace_bytes(M, N, K) bytes (0 when K
- * fits one workgroup), 16-byte aligned. */
+ * fits one workgroup), 16-byte aligned.
+ * lvllm_gemm_w8a8_int8 (csrc/int8_tiled_gemm.hip): the same result from the same operands for ANY M >= 1 -- the
+ * LDS-tiled, operand-reusing kernel for prefill batches (meant for M > 64; without bias bit for bit the decode
+ * kernel's output).  Same conditions: N % 16 == 0, K % 64 == 0, K < 131072, N * K < 2^32 - 16, ldx >= K, ldx % 16 ==
+ * 0, (M - 1) * ldx + K < 2^31, x_q / w_packed / w_scale 16-byte aligned, y 8-byte aligned; returns 3 and launches
+ * nothing outside the envelope.  workspace: int32 split-K partials for launches with fewer output tiles than CUs,
+ * lvllm_gemm_w8a8_int8_workspace_bytes(M, N, K) bytes (0 when K is not split), 16-byte aligned; ask again after
+ * lvllm_set_tuning("gemm_workgroups", ...), which the split follows. */
 int lvllm_static_scaled_int8_quant(void* out, const void* input, const float* scale, int64_t num_tokens,
                                    int hidden_size, int dtype, void* stream);
 int lvllm_dynamic_scaled_int8_quant(void* out, float* scales, const void* input, int64_t num_tokens, int hidden_size,
@@ -598,6 +607,10 @@ int64_t lvllm_skinny_gemm_w8a8_int8_workspace_bytes(int M, int N, int K);
 int lvllm_skinny_gemm_w8a8_int8(void* y, const void* x_q, const void* w_packed, const float* x_scale,
                                 const float* w_scale, const void* bias, int M, int N, int K, int64_t ldx, int dtype,
                                 void* workspace, int64_t workspace_bytes, void* stream);
+int64_t lvllm_gemm_w8a8_int8_workspace_bytes(int M, int N, int K);
+int lvllm_gemm_w8a8_int8(void* y, const void* x_q, const void* w_packed, const float* x_scale, const float* w_scale,
+                         const void* bias, int M, int N, int K, int64_t ldx, int dtype, void* workspace,
+                         int64_t workspace_bytes, void* stream);
 
 /* ---- device queries (csrc/cuda_utils.h, torch_bindings.cpp:271-279) ------- */
 int64_t lvllm_get_device_attribute(int64_t attribute, int64_t device_id);

@@ -33,6 +33,7 @@ HIP_SOURCES = [
     "skinny_gemm.hip",
     "awq_gemm.hip",
     "int8_gemm.hip",
+    "int8_tiled_gemm.hip",
     "prefill_attention.hip",
     "prepare_inputs.hip",
     "fp8_quant.hip",

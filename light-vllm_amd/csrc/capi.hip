@@ -71,6 +71,9 @@ extern "C" int lvllm_set_tuning(const char* key, int value) {
   } else if (k == "prefill_chunk_max_avg_x8") {
     LV_CHECK(value >= 8, "prefill_chunk_max_avg_x8 must be at least 8 (one token per sequence)");
     lvllm::tuning().prefill_chunk_max_avg_x8 = value;
+  } else if (k == "int8_tiled_min_rows") {
+    LV_CHECK(value >= 1, "int8_tiled_min_rows must be positive (a huge value: never)");
+    lvllm::tuning().int8_tiled_min_rows = value;
   } else {
     LV_CHECK(false, "unknown tuning key '" + k + "'");
   }
@@ -96,6 +99,7 @@ extern "C" int lvllm_get_tuning(const char* key, int* value) {
   else if (k == "prefill_mfma32_min_query") *value = t.prefill_mfma32_min_query;
   else if (k == "prefill_chunk_max_query") *value = t.prefill_chunk_max_query;
   else if (k == "prefill_chunk_max_avg_x8") *value = t.prefill_chunk_max_avg_x8;
+  else if (k == "int8_tiled_min_rows") *value = t.int8_tiled_min_rows;
   else LV_CHECK(false, "unknown tuning key '" + k + "'");
   return 0;
 }

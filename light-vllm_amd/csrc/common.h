@@ -28,6 +28,7 @@ void set_error(const std::string& msg);
 //   prefill_mfma32_min_query   see Tuning
 //   prefill_chunk_max_query, prefill_chunk_max_avg_x8    see Tuning
 //   varlen_dense     see Tuning
+//   int8_tiled_min_rows    see Tuning
 struct Tuning {
   int gemm_workgroups = 256;
   int gemm_workgroups_wide = 0;  // for projections with >= gemm_wide_min_tiles n-tiles; 0 = as above
@@ -54,6 +55,10 @@ struct Tuning {
   int prefill_chunk_max_avg_x8 = 16;  // at most max_avg_x8 / 8 = 2 query tokens per sequence on average, no chunk
                                       // longer than max_query) take the decode-style walk of prefill_chunk.h (plain
                                       // causal, head size 64 / 128, 16-bit cache); max_query 0 = never
+  int int8_tiled_min_rows = 256;  // W8A8 int8 linear: launches with at least this many rows take the LDS-tiled kernel
+                                  // (int8_tiled_gemm.hip), fewer run the weight-streaming kernel in chunks of 64 rows
+                                  // (at 128 rows the chunks are still level on qkv: profiles/int8_tiled_gemm.md); a huge
+                                  // value = always the chunks
 };
 Tuning& tuning();
 

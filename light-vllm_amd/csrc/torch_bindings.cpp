@@ -1263,12 +1263,12 @@ torch::Tensor int8_scale_vector(const torch::Tensor& s, int64_t n, const char* w
   return s.numel() == n ? s.reshape({n}).contiguous() : s.reshape({1}).expand({n}).contiguous();
 }
 
-// y [M, N] (contiguous, bf16 / f16) = sx[m] * (sw[n] * (x_q . Wq^T)[m, n]) (+ bias) from the packed weight.  Above 64
-// rows the same kernel runs over chunks of 64 rows: exact, hence equal row for row to the <= 64 path, but the weights
-// stream once per chunk -- a correctness path.
+// y [M, N] (contiguous, bf16 / f16) = sx[m] * (sw[n] * (x_q . Wq^T)[m, n]) (+ bias) from the packed weight.  From
+// tuning "int8_tiled_min_rows" rows on (or always, with `tiled`) the LDS-tiled kernel reads the weights once per
+// launch; below, the streaming kernel runs over chunks of 64 rows.  Both are exact, hence equal without bias.
 void int8_linear_into(torch::Tensor& y, const torch::Tensor& x_q_in, const torch::Tensor& w_packed,
                       const torch::Tensor& x_scale, const torch::Tensor& w_scale, int64_t N, int64_t K,
-                      const std::optional<torch::Tensor>& bias, const char* op) {
+                      const std::optional<torch::Tensor>& bias, const char* op, bool tiled = false) {
   LV_CHECK_DEVICE(x_q_in);
   LV_CHECK_DEVICE(w_packed);
   TORCH_CHECK(x_q_in.dim() == 2 && x_q_in.size(1) == K && x_q_in.scalar_type() == at::kChar, op, ": x_q must be [M, K] int8");
@@ -1286,10 +1286,23 @@ void int8_linear_into(torch::Tensor& y, const torch::Tensor& x_q_in, const torch
                           ((uintptr_t)x_q_in.data_ptr() & 15) == 0;
   const torch::Tensor x_q = strided_ok ? x_q_in : x_q_in.contiguous();
   const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(device_of(x_q));
-  const int64_t ws_bytes = lvllm_skinny_gemm_w8a8_int8_workspace_bytes((int)std::min<int64_t>(M, 64), (int)N, (int)K);
+  TORCH_CHECK(M < ((int64_t)1 << 31), op, ": too many rows");
+  int min_rows = 0;
+  check(lvllm_get_tuning("int8_tiled_min_rows", &min_rows));
+  // one descriptor spans all rows of the tiled launch: an X that reaches past 2 GiB stays with the 64-row chunks,
+  // each of which has a descriptor of its own
+  tiled = tiled || (M >= min_rows && (M - 1) * x_q.stride(0) + K < ((int64_t)1 << 31));
+  const int64_t ws_bytes = tiled ? lvllm_gemm_w8a8_int8_workspace_bytes((int)M, (int)N, (int)K)
+                                 : lvllm_skinny_gemm_w8a8_int8_workspace_bytes((int)std::min<int64_t>(M, 64), (int)N, (int)K);
   torch::Tensor ws;
   if (ws_bytes > 0) ws = torch::empty({ws_bytes / 4}, x_q.options().dtype(torch::kInt));
   const int dt = y.scalar_type() == at::kBFloat16 ? LVLLM_BF16 : LVLLM_F16;
+  if (tiled) {
+    check(lvllm_gemm_w8a8_int8(y.data_ptr(), x_q.data_ptr(), w_packed.data_ptr(), sx.data_ptr<float>(),
+                               sw.data_ptr<float>(), bias ? bias->data_ptr() : nullptr, (int)M, (int)N, (int)K,
+                               x_q.stride(0), dt, ws_bytes > 0 ? ws.data_ptr() : nullptr, ws_bytes, current_stream(x_q)));
+    return;
+  }
   for (int64_t m0 = 0; m0 < M; m0 += 64) {
     const int64_t rows = std::min<int64_t>(64, M - m0);
     check(lvllm_skinny_gemm_w8a8_int8((char*)y.data_ptr() + m0 * N * 2, (const char*)x_q.data_ptr() + m0 * x_q.stride(0),
@@ -1306,6 +1319,17 @@ torch::Tensor skinny_linear_w8a8_int8(const torch::Tensor& x_q, const torch::Ten
   TORCH_CHECK(x_q.dim() == 2, "skinny_linear_w8a8_int8: x_q must be [M, K] int8");
   auto y = torch::empty({x_q.size(0), N}, x_q.options().dtype(out_dtype));
   int8_linear_into(y, x_q, w_packed, x_scale, w_scale, N, K, bias, "skinny_linear_w8a8_int8");
+  return y;
+}
+
+// the tiled kernel at any M: what tests and benchmarks address directly
+torch::Tensor linear_w8a8_int8_tiled(const torch::Tensor& x_q, const torch::Tensor& w_packed,
+                                     const torch::Tensor& x_scale, const torch::Tensor& w_scale, int64_t N, int64_t K,
+                                     const std::optional<torch::Tensor>& bias, at::ScalarType out_dtype) {
+  LV_CHECK_DEVICE(x_q);
+  TORCH_CHECK(x_q.dim() == 2, "linear_w8a8_int8_tiled: x_q must be [M, K] int8");
+  auto y = torch::empty({x_q.size(0), N}, x_q.options().dtype(out_dtype));
+  int8_linear_into(y, x_q, w_packed, x_scale, w_scale, N, K, bias, "linear_w8a8_int8_tiled", true);
   return y;
 }
 
@@ -1483,6 +1507,9 @@ TORCH_LIBRARY(_C_amd, amd) {
   amd.def("skinny_linear_w8a8_int8(Tensor x_q, Tensor w_packed, Tensor x_scale, Tensor w_scale, int N, int K, "
           "Tensor? bias, ScalarType out_dtype) -> Tensor");
   amd.impl("skinny_linear_w8a8_int8", torch::kCUDA, &skinny_linear_w8a8_int8);
+  amd.def("linear_w8a8_int8_tiled(Tensor x_q, Tensor w_packed, Tensor x_scale, Tensor w_scale, int N, int K, "
+          "Tensor? bias, ScalarType out_dtype) -> Tensor");
+  amd.impl("linear_w8a8_int8_tiled", torch::kCUDA, &linear_w8a8_int8_tiled);
   amd.def("gelu(Tensor! out, Tensor x) -> ()");
   amd.impl("gelu", torch::kCUDA, &gelu);
   amd.def("add_layer_norm(Tensor! out, Tensor x, Tensor? y, Tensor weight, Tensor bias, float epsilon) -> ()");

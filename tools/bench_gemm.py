@@ -174,6 +174,78 @@ def int8_leg(out_path):
             f.write("\n".join(lines) + "\n")
 
 
+def int8_prefill_leg(out_path):
+    """--int8-prefill [out.md]: (a) the LDS-tiled W8A8 int8 GEMM (linear_w8a8_int8_tiled) against (b) the 64-row chunks
+    of the streaming kernel (skinny_linear_w8a8_int8 with int8_tiled_min_rows above M: what the linear did before the
+    tiled kernel) and (c) torch.matmul in bf16, what the 16-bit model pays.  Same process, weights rotate through
+    > 0.5 GB per format, 3 warm-up rounds, then REGIONS regions of PER rounds, the legs alternating launch by launch
+    inside a round; a region's figure is the median of its device-event times and every region is listed.  The tuning
+    key is set once, outside the timed spans.  Op/s from 2 M N K.  INT8_PEAK_TOPS=<dense int8 peak> adds the share of
+    that peak."""
+    REGIONS = 5
+    shapes = [("qkv", 6144, 4096), ("o", 4096, 4096), ("gate_up", 28672, 4096), ("down", 4096, 14336)]
+    fmt = lambda r: " ".join(f"{t:.0f}" for t in r)  # noqa: E731
+    med = lambda r: sorted(r)[len(r) // 2]  # noqa: E731
+    peak = float(os.environ.get("INT8_PEAK_TOPS", "0"))
+    default_rows = torch.ops._C_amd.get_tuning("int8_tiled_min_rows")
+    lines = ["| shape | M | tiled us (regions) | chunks of 64 us (regions) | bf16 matmul us (regions) | tiled Top/s" +
+             (" | of peak" if peak else "") + " | chunks Top/s | bf16 Tflop/s | tiled vs chunks |",
+             "|---|---|---|---|---|---|---|---|---|" + ("---|" if peak else "")]
+    torch.ops._C_amd.set_tuning("int8_tiled_min_rows", 1 << 30)  # skinny_linear_w8a8_int8 = the chunks from here on
+    for name, N, K in shapes:
+        w8 = torch.ops._C_amd.int8_pack(torch.randint(-128, 128, (N, K), device=dev, dtype=torch.int8))
+        n8, n16 = int(0.55e9 // (N * K)) + 1, int(0.55e9 // (N * K * 2)) + 1
+        w8s = [w8.clone() for _ in range(n8)]
+        w16s = [(torch.randn(N, K, device=dev) * 0.02).to(torch.bfloat16) for _ in range(n16)]
+        sw = torch.rand(N, device=dev) * 1e-3 + 1e-4
+        for M in (128, 256, 512, 2048, 8192):
+            PER = 20 if M <= 512 else 6
+            xq = torch.randint(-128, 128, (M, K), device=dev, dtype=torch.int8)
+            x16 = (torch.randn(M, K, device=dev) * 0.5).to(torch.bfloat16)
+            sx = torch.rand(M, device=dev) * 1e-2 + 1e-3
+            fs = [lambda i: torch.ops._C_amd.linear_w8a8_int8_tiled(xq, w8s[i % n8], sx, sw, N, K, None, torch.bfloat16),
+                  lambda i: torch.ops._C_amd.skinny_linear_w8a8_int8(xq, w8s[i % n8], sx, sw, N, K, None, torch.bfloat16),
+                  lambda i: torch.matmul(x16, w16s[i % n16].t())]
+            assert torch.equal(fs[0](0), fs[1](0))  # same bits, or no table
+            for i in range(3):
+                for f in fs:
+                    f(i)
+            torch.cuda.synchronize()
+            regions, it = [[] for _ in fs], 0
+            for _ in range(REGIONS):
+                evs = []
+                for _ in range(PER):
+                    e = [torch.cuda.Event(enable_timing=True) for _ in range(len(fs) + 1)]
+                    e[0].record()
+                    for j, f in enumerate(fs):
+                        f(it)
+                        e[j + 1].record()
+                    evs.append(e)
+                    it += 1
+                torch.cuda.synchronize()
+                for j in range(len(fs)):
+                    regions[j].append(med([e[j].elapsed_time(e[j + 1]) * 1e3 for e in evs]))
+            rt, rc, rb = regions
+            ops = 2.0 * M * N * K
+            verdict = ("faster beyond the spread" if max(rt) < min(rc) else
+                       "SLOWER beyond the spread" if min(rt) > max(rc) else "within the spread")
+            lines.append(f"| {name} {N}x{K} | {M} | {med(rt):.1f} ({fmt(rt)}) | {med(rc):.1f} ({fmt(rc)}) | "
+                         f"{med(rb):.1f} ({fmt(rb)}) | {ops / med(rt) / 1e6:.0f}" +
+                         (f" | {ops / med(rt) / 1e6 / peak:.0%}" if peak else "") +
+                         f" | {ops / med(rc) / 1e6:.0f} | {ops / med(rb) / 1e6:.0f} | {med(rc) / med(rt):.2f}x, {verdict} |")
+            print(lines[-1], flush=True)
+        del w8s, w16s
+        torch.cuda.empty_cache()
+    torch.ops._C_amd.set_tuning("int8_tiled_min_rows", default_rows)
+    if out_path:
+        with open(out_path, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if len(sys.argv) > 1 and sys.argv[1] == "--int8-prefill":
+    int8_prefill_leg(sys.argv[2] if len(sys.argv) > 2 else None)
+    sys.exit(0)
+
 if len(sys.argv) > 1 and sys.argv[1] == "--int8":
     int8_leg(sys.argv[2] if len(sys.argv) > 2 else None)
     sys.exit(0)
