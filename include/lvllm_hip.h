@@ -66,8 +66,10 @@ const char* lvllm_version(void);
  * tokens whose grid fits the CUs at once; 0 = never), "varlen_dense" (1 | 0: lvllm_varlen_attention's long plain
  * launches read key/value in place instead of packing them first), "varlen_dense_waves" (waves per workgroup of that
  * launch: 8, 4, or 0 = by the longest sequence), "int8_tiled_min_rows" (the torch layer's W8A8 int8 linear: row count
- * from which the LDS-tiled kernel runs instead of 64-row chunks of the streaming one).  lvllm_get_tuning reads a knob
- * back. */
+ * from which the LDS-tiled kernel runs instead of 64-row chunks of the streaming one), "w4_tiled_min_rows" and
+ * "w4_tiled_max_rows" (the torch layer's W4A16 linear above 64 rows: the range of row counts that take the LDS-tiled
+ * kernel instead of dequantising the packed weight for the library GEMM; min_rows huge = never).  lvllm_get_tuning
+ * reads a knob back. */
 int lvllm_set_tuning(const char* key, int value);
 int lvllm_get_tuning(const char* key, int* value);
 
@@ -565,7 +567,16 @@ int lvllm_rope_cache_paged_attention_q(
  * lvllm_skinny_gemm_w4a16: y [M, N] = T(x . Wd (+ bias)), fp32 accumulation, x [M <= 64, K] (rows ldx elements
  * apart) -- ops.awq_gemm (gemm_kernels.cu:469-471) for decode batches.  K % 128 == 0 in addition to the conditions
  * of lvllm_awq_pack; returns 3 and launches nothing outside the envelope.  workspace: fp32 split-K partials,
- * lvllm_skinny_gemm_w4a16_workspace_bytes(M, N, K) bytes (0 when K fits one workgroup). */
+ * lvllm_skinny_gemm_w4a16_workspace_bytes(M, N, K) bytes (0 when K fits one workgroup).
+ * lvllm_gemm_w4a16 (csrc/awq_tiled_gemm.hip): the same product from the same packed pair for ANY M >= 1 -- the
+ * LDS-tiled kernel for prefill batches (meant for M > 64): x through LDS, the weights dequantised in registers with
+ * the decode kernel's arithmetic (Wd is the same bits; the fp32 sums are formed in another order).  N % 16 == 0,
+ * K % 128 == 0, G in {32, 64, 128}, packed weight below 4 GiB, ldx >= K, ldx % 8 == 0, ((M - 1) * ldx + K) * 2 <
+ * 2^31, x / w4_packed / meta 16-byte aligned, y 8-byte aligned; returns 3 and launches nothing outside the envelope.
+ * workspace: fp32 split-K partials for launches with fewer output tiles than the device holds workgroups,
+ * lvllm_gemm_w4a16_workspace_bytes(M, N, K) bytes (0 when K is not split), 16-byte aligned; ask again after
+ * lvllm_set_tuning("gemm_workgroups", ...), which the split follows.  The partials are summed in a fixed order: the
+ * result is deterministic for a shape and tuning, but may differ in the last bit between two splits. */
 int64_t lvllm_awq_packed_bytes(int N, int K);
 int64_t lvllm_awq_meta_bytes(int N, int K, int group_size);
 int lvllm_awq_pack(void* w4_packed, void* meta, const void* qweight, const void* qzeros, const void* scales, int N,
@@ -578,6 +589,10 @@ int64_t lvllm_skinny_gemm_w4a16_workspace_bytes(int M, int N, int K);
 int lvllm_skinny_gemm_w4a16(void* y, const void* x, const void* w4_packed, const void* meta, const void* bias, int M,
                             int N, int K, int group_size, int64_t ldx, int dtype, void* workspace,
                             int64_t workspace_bytes, void* stream);
+int64_t lvllm_gemm_w4a16_workspace_bytes(int M, int N, int K);
+int lvllm_gemm_w4a16(void* y, const void* x, const void* w4_packed, const void* meta, const void* bias, int M, int N,
+                     int K, int group_size, int64_t ldx, int dtype, void* workspace, int64_t workspace_bytes,
+                     void* stream);
 
 /* ---- W8A8 int8: per-token x per-channel scales (csrc/int8_quant.hip, csrc/int8_gemm.hip) ----------------------
  * The compressed-tensors / SmoothQuant scheme of the reference (w8a8_utils.py:192-209, int8_quant_kernels.cu,

@@ -32,6 +32,7 @@ HIP_SOURCES = [
     "attention_f16.hip",
     "skinny_gemm.hip",
     "awq_gemm.hip",
+    "awq_tiled_gemm.hip",
     "int8_gemm.hip",
     "int8_tiled_gemm.hip",
     "prefill_attention.hip",

@@ -74,6 +74,12 @@ extern "C" int lvllm_set_tuning(const char* key, int value) {
   } else if (k == "int8_tiled_min_rows") {
     LV_CHECK(value >= 1, "int8_tiled_min_rows must be positive (a huge value: never)");
     lvllm::tuning().int8_tiled_min_rows = value;
+  } else if (k == "w4_tiled_min_rows") {
+    LV_CHECK(value >= 1, "w4_tiled_min_rows must be positive (a huge value: never)");
+    lvllm::tuning().w4_tiled_min_rows = value;
+  } else if (k == "w4_tiled_max_rows") {
+    LV_CHECK(value >= 0, "w4_tiled_max_rows must be non-negative (0: never)");
+    lvllm::tuning().w4_tiled_max_rows = value;
   } else {
     LV_CHECK(false, "unknown tuning key '" + k + "'");
   }
@@ -100,6 +106,8 @@ extern "C" int lvllm_get_tuning(const char* key, int* value) {
   else if (k == "prefill_chunk_max_query") *value = t.prefill_chunk_max_query;
   else if (k == "prefill_chunk_max_avg_x8") *value = t.prefill_chunk_max_avg_x8;
   else if (k == "int8_tiled_min_rows") *value = t.int8_tiled_min_rows;
+  else if (k == "w4_tiled_min_rows") *value = t.w4_tiled_min_rows;
+  else if (k == "w4_tiled_max_rows") *value = t.w4_tiled_max_rows;
   else LV_CHECK(false, "unknown tuning key '" + k + "'");
   return 0;
 }

@@ -29,6 +29,7 @@ void set_error(const std::string& msg);
 //   prefill_chunk_max_query, prefill_chunk_max_avg_x8    see Tuning
 //   varlen_dense     see Tuning
 //   int8_tiled_min_rows    see Tuning
+//   w4_tiled_min_rows, w4_tiled_max_rows    see Tuning
 struct Tuning {
   int gemm_workgroups = 256;
   int gemm_workgroups_wide = 0;  // for projections with >= gemm_wide_min_tiles n-tiles; 0 = as above
@@ -59,6 +60,11 @@ struct Tuning {
                                   // (int8_tiled_gemm.hip), fewer run the weight-streaming kernel in chunks of 64 rows
                                   // (at 128 rows the chunks are still level on qkv: profiles/int8_tiled_gemm.md); a huge
                                   // value = always the chunks
+  int w4_tiled_min_rows = 65;   // W4A16 (AWQ) linear above the streaming kernel's 64 rows: launches with min_rows <= M <=
+  int w4_tiled_max_rows = 512;  // max_rows take the LDS-tiled kernel (awq_tiled_gemm.hip), the others dequantise the
+                                // packed weight and call the library GEMM.  Measured (profiles/awq_tiled_gemm.md): faster
+                                // beyond the spread on all four 8B projections at 65 .. 512 rows, slower on two at 1024;
+                                // min_rows huge = never the tiled kernel
 };
 Tuning& tuning();
 

@@ -1152,26 +1152,50 @@ torch::Tensor awq_dequantize(const torch::Tensor& qweight, const torch::Tensor& 
   return out;
 }
 
-// y [M, N] = x . Wd (+ bias) from the packed pair of awq_pack: the streaming kernel at <= 64 rows of its envelope,
-// otherwise Wd from the packed pair and the library GEMM, as the reference does for large batches (awq.py:164-169)
-torch::Tensor skinny_linear_w4a16(const torch::Tensor& x, const torch::Tensor& w4_packed, const torch::Tensor& meta,
-                                  int64_t N, int64_t K, int64_t group_size, const std::optional<torch::Tensor>& bias) {
+// the argument checks of the two W4A16 linears below
+void w4a16_check(const torch::Tensor& x, const torch::Tensor& w4_packed, const torch::Tensor& meta, int64_t N,
+                 int64_t K, int64_t group_size, const std::optional<torch::Tensor>& bias, const char* op) {
   LV_CHECK_DEVICE(x);
   LV_CHECK_DEVICE(w4_packed);
   LV_CHECK_DEVICE(meta);
   TORCH_CHECK(x.dim() == 2 && x.size(1) == K && x.stride(1) == 1 &&
                   (x.scalar_type() == at::kHalf || x.scalar_type() == at::kBFloat16),
-              "skinny_linear_w4a16: x must be [M, K] f16 / bf16");
+              op, ": x must be [M, K] f16 / bf16");
   TORCH_CHECK(N > 0 && K > 0 && N % 16 == 0 && (group_size == 32 || group_size == 64 || group_size == 128) &&
                   K % group_size == 0,
-              "skinny_linear_w4a16: N % 16 == 0, group_size 32 / 64 / 128, K % group_size == 0");
+              op, ": N % 16 == 0, group_size 32 / 64 / 128, K % group_size == 0");
   TORCH_CHECK(w4_packed.is_contiguous() && meta.is_contiguous() &&
                   w4_packed.numel() * w4_packed.element_size() == lvllm_awq_packed_bytes((int)N, (int)K) &&
                   meta.numel() * meta.element_size() == lvllm_awq_meta_bytes((int)N, (int)K, (int)group_size),
-              "skinny_linear_w4a16: w4_packed / meta do not have the size awq_pack gives for this N, K, group_size");
+              op, ": w4_packed / meta do not have the size awq_pack gives for this N, K, group_size");
   TORCH_CHECK(!bias || (bias->is_cuda() && bias->is_contiguous() && bias->numel() == N &&
                         bias->scalar_type() == x.scalar_type()),
-              "skinny_linear_w4a16: bias must be [N] of x's dtype");
+              op, ": bias must be [N] of x's dtype");
+}
+
+// the LDS-tiled kernel into y [M, N] (M >= 1), split-K workspace allocated here; 0, or 3 outside its envelope
+int w4a16_tiled_into(torch::Tensor& y, const torch::Tensor& x, const torch::Tensor& w4_packed,
+                     const torch::Tensor& meta, int64_t N, int64_t K, int64_t group_size,
+                     const std::optional<torch::Tensor>& bias, const char* op) {
+  const int64_t M = x.size(0);
+  const int64_t ws_bytes = lvllm_gemm_w4a16_workspace_bytes((int)M, (int)N, (int)K);
+  torch::Tensor ws;
+  if (ws_bytes > 0) ws = torch::empty({ws_bytes / 4}, x.options().dtype(torch::kFloat));
+  const int rc = lvllm_gemm_w4a16(y.data_ptr(), x.data_ptr(), w4_packed.data_ptr(), meta.data_ptr(),
+                                  bias ? bias->data_ptr() : nullptr, (int)M, (int)N, (int)K, (int)group_size,
+                                  x.stride(0), dtype_code(x, op), ws_bytes > 0 ? ws.data_ptr() : nullptr, ws_bytes,
+                                  current_stream(x));
+  TORCH_CHECK(rc == 0 || rc == 3, lvllm_last_error());
+  return rc;
+}
+
+// y [M, N] = x . Wd (+ bias) from the packed pair of awq_pack.  ONE place decides the route: the streaming kernel at
+// <= 64 rows of its envelope; the LDS-tiled kernel (awq_tiled_gemm.hip) for tuning "w4_tiled_min_rows" <= M <=
+// "w4_tiled_max_rows" inside its envelope; otherwise Wd from the packed pair and the library GEMM, as the reference
+// does for large batches (awq.py:164-169)
+torch::Tensor skinny_linear_w4a16(const torch::Tensor& x, const torch::Tensor& w4_packed, const torch::Tensor& meta,
+                                  int64_t N, int64_t K, int64_t group_size, const std::optional<torch::Tensor>& bias) {
+  w4a16_check(x, w4_packed, meta, N, K, group_size, bias, "skinny_linear_w4a16");
   const int64_t M = x.size(0);
   const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(device_of(x));
   const int dt = dtype_code(x, "skinny_linear_w4a16");
@@ -1187,12 +1211,32 @@ torch::Tensor skinny_linear_w4a16(const torch::Tensor& x, const torch::Tensor& w
                                            current_stream(x));
     if (rc == 0) return y;
     TORCH_CHECK(rc == 3, lvllm_last_error());  // 3: strides / alignment outside the envelope -> the route below
+  } else if (K % 128 == 0) {
+    int min_rows = 0, max_rows = 0;
+    check(lvllm_get_tuning("w4_tiled_min_rows", &min_rows));
+    check(lvllm_get_tuning("w4_tiled_max_rows", &max_rows));
+    if (M >= min_rows && M <= max_rows) {
+      auto y = torch::empty({M, N}, x.options());
+      if (w4a16_tiled_into(y, x, w4_packed, meta, N, K, group_size, bias, "skinny_linear_w4a16") == 0) return y;
+    }  // 3: strides / alignment outside the envelope -> the route below
   }
   auto wd = torch::empty({K, N}, x.options());
   check(lvllm_awq_dequantize_packed(wd.data_ptr(), w4_packed.data_ptr(), meta.data_ptr(), (int)N, (int)K,
                                     (int)group_size, dt, current_stream(x)));
   auto y = at::matmul(x, wd);
   if (bias) y.add_(*bias);
+  return y;
+}
+
+// Always the LDS-tiled kernel, any M >= 1; raises outside its envelope (K % 128, row stride, alignment)
+torch::Tensor linear_w4a16_tiled(const torch::Tensor& x, const torch::Tensor& w4_packed, const torch::Tensor& meta,
+                                 int64_t N, int64_t K, int64_t group_size, const std::optional<torch::Tensor>& bias) {
+  w4a16_check(x, w4_packed, meta, N, K, group_size, bias, "linear_w4a16_tiled");
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(device_of(x));
+  auto y = torch::empty({x.size(0), N}, x.options());
+  if (x.size(0) == 0) return y;
+  TORCH_CHECK(w4a16_tiled_into(y, x, w4_packed, meta, N, K, group_size, bias, "linear_w4a16_tiled") == 0,
+              lvllm_last_error());
   return y;
 }
 
@@ -1501,6 +1545,9 @@ TORCH_LIBRARY(_C_amd, amd) {
   amd.def("skinny_linear_w4a16(Tensor x, Tensor w4_packed, Tensor meta, int N, int K, int group_size, "
           "Tensor? bias) -> Tensor");
   amd.impl("skinny_linear_w4a16", torch::kCUDA, &skinny_linear_w4a16);
+  amd.def("linear_w4a16_tiled(Tensor x, Tensor w4_packed, Tensor meta, int N, int K, int group_size, "
+          "Tensor? bias) -> Tensor");
+  amd.impl("linear_w4a16_tiled", torch::kCUDA, &linear_w4a16_tiled);
   // W8A8 int8: pack once after loading, then stream the packed weight per step with pre-quantised activations
   amd.def("int8_pack(Tensor w_q) -> Tensor");
   amd.impl("int8_pack", torch::kCUDA, &int8_pack);

@@ -1,12 +1,12 @@
 """AWQ (4-bit group-quantised weights, 16-bit activations) of the reference
-(light_vllm/backends/quantization/awq.py): the config, the load-time repack for the gfx950 weight-streaming
-kernel (csrc/awq_gemm.hip), the linear, and a plain quantiser that produces checkpoint-layout tensors."""
+(light_vllm/backends/quantization/awq.py): the config, the load-time repack for the gfx950 kernels
+(csrc/awq_gemm.hip for decode, csrc/awq_tiled_gemm.hip for prefill), the linear, and a plain quantiser that produces
+checkpoint-layout tensors."""
 from typing import Any, Dict, List, Optional, Tuple
 
 import torch
 
 AWQ_ORDER = (0, 2, 4, 6, 1, 3, 5, 7)  # nibble i of a packed word holds column 8 j + AWQ_ORDER[i]
-SKINNY_MAX_ROWS = 64
 
 
 class AWQConfig:
@@ -88,14 +88,10 @@ def pack_awq_weight(qweight: torch.Tensor, qzeros: torch.Tensor, scales: torch.T
 
 def apply_awq_linear(x: torch.Tensor, w4_packed: torch.Tensor, meta: torch.Tensor, qweight: torch.Tensor,
                      qzeros: torch.Tensor, scales: torch.Tensor, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """awq.py:153-175 of the reference: the streaming kernel for decode batches (<= 64 rows), dequantise + library
-    GEMM above (the reference switches at 256 tokens; here at the kernel's envelope)."""
+    """awq.py:153-175 of the reference, on the packed pair for every row count: skinny_linear_w4a16 decides the route
+    (the streaming kernel for decode batches of <= 64 rows, the LDS-tiled kernel for prefill batches inside the tuning
+    range w4_tiled_min_rows .. w4_tiled_max_rows, dequantise-from-packed + library GEMM elsewhere).  The checkpoint
+    tensors only give the shape here."""
     K, N = qweight.shape[0], scales.shape[1]
-    x2 = x.reshape(-1, K)
-    if x2.shape[0] <= SKINNY_MAX_ROWS:
-        out = torch.ops._C_amd.skinny_linear_w4a16(x2, w4_packed, meta, N, K, K // scales.shape[0], bias)
-    else:
-        out = torch.matmul(x2, torch.ops._C.awq_dequantize(qweight, scales, qzeros, 0, 0, 0))
-        if bias is not None:
-            out.add_(bias)
+    out = torch.ops._C_amd.skinny_linear_w4a16(x.reshape(-1, K), w4_packed, meta, N, K, K // scales.shape[0], bias)
     return out.reshape(x.shape[:-1] + (N,))

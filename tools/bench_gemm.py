@@ -242,6 +242,79 @@ def int8_prefill_leg(out_path):
             f.write("\n".join(lines) + "\n")
 
 
+def awq_prefill_leg(out_path):
+    """--awq-prefill [out.md]: (a) the LDS-tiled W4A16 GEMM (linear_w4a16_tiled) against (b) dequantise-from-packed +
+    library GEMM (skinny_linear_w4a16 with w4_tiled_min_rows huge: what the linear did before the tiled kernel) and
+    (c) torch.matmul in bf16, what the 16-bit model pays (a goal, not a gate).  G = 128, bf16.  The method of
+    --int8-prefill: same process, weights rotate through > 0.5 GB per format, 3 warm-up rounds, then REGIONS regions of
+    PER rounds, the legs alternating launch by launch inside a round; a region's figure is the median of its
+    device-event times and every region is listed.  The tuning key is set once, outside the timed spans.  Before
+    timing, each row asserts the tiled output within the kernel family's tolerance of the library route's."""
+    REGIONS, G = 5, 128
+    shapes = [("qkv", 6144, 4096), ("o", 4096, 4096), ("gate_up", 28672, 4096), ("down", 4096, 14336)]
+    fmt = lambda r: " ".join(f"{t:.0f}" for t in r)  # noqa: E731
+    med = lambda r: sorted(r)[len(r) // 2]  # noqa: E731
+    default_rows = torch.ops._C_amd.get_tuning("w4_tiled_min_rows")
+    lines = ["| shape | M | tiled us (regions) | dequantise + library us (regions) | bf16 matmul us (regions) | "
+             "tiled Tflop/s | dequantise + library Tflop/s | bf16 Tflop/s | tiled vs dequantise + library |",
+             "|---|---|---|---|---|---|---|---|---|"]
+    torch.ops._C_amd.set_tuning("w4_tiled_min_rows", 1 << 30)  # skinny_linear_w4a16 = the library route from here on
+    for name, N, K in shapes:
+        qw = torch.randint(-2 ** 31, 2 ** 31, (K, N // 8), device=dev, dtype=torch.int64).to(torch.int32)
+        qz = torch.randint(-2 ** 31, 2 ** 31, (K // G, N // 8), device=dev, dtype=torch.int64).to(torch.int32)
+        sc = (torch.rand(K // G, N, device=dev) * 0.01 + 1e-3).to(torch.bfloat16)
+        w4, meta = torch.ops._C_amd.awq_pack(qw, qz, sc)
+        del qw, qz
+        n4, n16 = int(0.55e9 // (w4.numel() * 4 + meta.numel() * 4)) + 1, int(0.55e9 // (N * K * 2)) + 1
+        w4s = [(w4.clone(), meta.clone()) for _ in range(n4)]
+        w16s = [(torch.randn(K, N, device=dev) * 0.02).to(torch.bfloat16) for _ in range(n16)]
+        for M in (65, 128, 256, 512, 1024, 2048, 8192):
+            PER = 20 if M <= 512 else 6
+            x = (torch.randn(M, K, device=dev) * 0.5).to(torch.bfloat16)
+            fs = [lambda i: torch.ops._C_amd.linear_w4a16_tiled(x, w4s[i % n4][0], w4s[i % n4][1], N, K, G, None),
+                  lambda i: torch.ops._C_amd.skinny_linear_w4a16(x, w4s[i % n4][0], w4s[i % n4][1], N, K, G, None),
+                  lambda i: torch.matmul(x, w16s[i % n16])]
+            yt, yl = fs[0](0).float(), fs[1](0).float()
+            assert (yt - yl).abs().max().item() <= 2 ** -6 * yl.abs().max().item() + 2e-3  # each within 2^-7 + 1e-3 of fp32
+            del yt, yl
+            for i in range(3):
+                for f in fs:
+                    f(i)
+            torch.cuda.synchronize()
+            regions, it = [[] for _ in fs], 0
+            for _ in range(REGIONS):
+                evs = []
+                for _ in range(PER):
+                    e = [torch.cuda.Event(enable_timing=True) for _ in range(len(fs) + 1)]
+                    e[0].record()
+                    for j, f in enumerate(fs):
+                        f(it)
+                        e[j + 1].record()
+                    evs.append(e)
+                    it += 1
+                torch.cuda.synchronize()
+                for j in range(len(fs)):
+                    regions[j].append(med([e[j].elapsed_time(e[j + 1]) * 1e3 for e in evs]))
+            rt, rl, rb = regions
+            flop = 2.0 * M * N * K
+            verdict = ("faster beyond the spread" if max(rt) < min(rl) else
+                       "SLOWER beyond the spread" if min(rt) > max(rl) else "within the spread")
+            lines.append(f"| {name} {N}x{K} | {M} | {med(rt):.1f} ({fmt(rt)}) | {med(rl):.1f} ({fmt(rl)}) | "
+                         f"{med(rb):.1f} ({fmt(rb)}) | {flop / med(rt) / 1e6:.0f} | {flop / med(rl) / 1e6:.0f} | "
+                         f"{flop / med(rb) / 1e6:.0f} | {med(rl) / med(rt):.2f}x, {verdict} |")
+            print(lines[-1], flush=True)
+        del w4s, w16s
+        torch.cuda.empty_cache()
+    torch.ops._C_amd.set_tuning("w4_tiled_min_rows", default_rows)
+    if out_path:
+        with open(out_path, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if len(sys.argv) > 1 and sys.argv[1] == "--awq-prefill":
+    awq_prefill_leg(sys.argv[2] if len(sys.argv) > 2 else None)
+    sys.exit(0)
+
 if len(sys.argv) > 1 and sys.argv[1] == "--int8-prefill":
     int8_prefill_leg(sys.argv[2] if len(sys.argv) > 2 else None)
     sys.exit(0)
