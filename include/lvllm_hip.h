@@ -68,8 +68,10 @@ const char* lvllm_version(void);
  * launch: 8, 4, or 0 = by the longest sequence), "int8_tiled_min_rows" (the torch layer's W8A8 int8 linear: row count
  * from which the LDS-tiled kernel runs instead of 64-row chunks of the streaming one), "w4_tiled_min_rows" and
  * "w4_tiled_max_rows" (the torch layer's W4A16 linear above 64 rows: the range of row counts that take the LDS-tiled
- * kernel instead of dequantising the packed weight for the library GEMM; min_rows huge = never).  lvllm_get_tuning
- * reads a knob back. */
+ * kernel instead of dequantising the packed weight for the library GEMM; min_rows huge = never), "fp8_tiled_min_rows"
+ * and "fp8_tiled_max_rows" (the Python layer's W8A8 fp8 linear, apply_fp8_linear with a packed weight: the range of
+ * row counts that quantise without padding and take the LDS-tiled kernel instead of torch._scaled_mm; min above max =
+ * never).  lvllm_get_tuning reads a knob back. */
 int lvllm_set_tuning(const char* key, int value);
 int lvllm_get_tuning(const char* key, int* value);
 
@@ -518,6 +520,23 @@ int lvllm_skinny_gemm_w8a8_ex(void* y, const void* x, const void* w_packed, cons
                               const float* x_scale, const float* w_scale, int M, int N, int K,
                               int64_t ldx, int dtype, int act, void* workspace,
                               int64_t workspace_bytes, void* stream);
+
+/* lvllm_gemm_w8a8_fp8 (csrc/fp8_tiled_gemm.hip): the W8A8 fp8 product for ANY M >= 1 -- the LDS-tiled,
+ * operand-reusing kernel for prefill batches (meant for M > 64) on v_mfma_f32_16x16x128_f8f6f4.  y [M, N] =
+ * T((acc * x_scale[m]) * w_scale[n] + bias[n]), acc = sum_k float(x_fp8[m, k]) * float(w8[n, k]) in fp32, the
+ * epilogue in fp32 in that order, one rounding to T = bf16 / f16.  x_fp8 [M, K] e4m3fn bytes ALREADY quantised
+ * (lvllm_*_scaled_fp8_quant), rows ldx BYTES apart; w_packed as for lvllm_skinny_gemm_w8a8; x_scale fp32 with
+ * x_scale_count = 1 or M entries, w_scale fp32 with w_scale_count = 1 or N entries (16-byte aligned when N); bias [N]
+ * of T or null.  N % 16 == 0, K % 64 == 0, N * K < 2^32 - 16, ldx >= K, ldx % 16 == 0, (M - 1) * ldx + K < 2^31,
+ * x_fp8 / w_packed 16-byte aligned, y 8-byte aligned; returns 3 and launches nothing outside the envelope.
+ * workspace: fp32 split-K partials for launches with fewer output tiles than the device holds workgroups,
+ * lvllm_gemm_w8a8_fp8_workspace_bytes(M, N, K) bytes (0 when K is not split), 16-byte aligned; ask again after
+ * lvllm_set_tuning("gemm_workgroups", ...), which the split follows.  The partials are summed in the order of the
+ * splits: the result is deterministic for a shape and tuning, but may differ in the last bit between two splits. */
+int64_t lvllm_gemm_w8a8_fp8_workspace_bytes(int M, int N, int K);
+int lvllm_gemm_w8a8_fp8(void* y, const void* x_fp8, const void* w_packed, const float* x_scale, const float* w_scale,
+                        int x_scale_count, int w_scale_count, const void* bias, int M, int N, int K, int64_t ldx,
+                        int dtype, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* W8A8 with activations that arrive ALREADY quantised: x_fp8 [M <= 32, K] bytes, rows ldx BYTES apart, =
  * static_scaled_fp8_quant(x, *x_scale) as written by the *_quant norm entries above or by this entry's SwiGLU epilogue.

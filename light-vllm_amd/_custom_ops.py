@@ -141,9 +141,11 @@ def scaled_int8_quant(input: torch.Tensor, scale: Optional[torch.Tensor] = None)
 
 def cutlass_scaled_mm(a: torch.Tensor, b: torch.Tensor, scale_a: torch.Tensor, scale_b: torch.Tensor,
                       out_dtype: torch.dtype, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """out = scale_a[m] * (scale_b[n] * (a . b)) + bias for int8 a [M, K] and b [K, N] (column-major, weight.t()),
-    int32 accumulation -- the reference's operator name, served by this package's HIP kernel; fp8 operands are
-    refused (quantization.apply_fp8_linear is their route)."""
+    """The reference's operator name, served by this package's HIP kernels, for a [M, K] and b [K, N] (column-major,
+    weight.t()) that are both int8 or both float8_e4m3fn.  int8: out = scale_a[m] * (scale_b[n] * (a . b)) + bias,
+    int32 accumulation.  fp8: out = ((a . b) * scale_a[m]) * scale_b[n] + bias, fp32 accumulation on the LDS-tiled
+    kernel (fp8_tiled_gemm.hip).  b is packed on every call; a host that keeps its weights packs once
+    (quantization.pack_int8_weight / pack_fp8_weight) and calls the linear ops."""
     out = torch.empty((a.shape[0], b.shape[1]), dtype=out_dtype, device=a.device)
     _C.cutlass_scaled_mm(out, a, b, scale_a, scale_b, bias)
     return out

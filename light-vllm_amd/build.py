@@ -35,6 +35,7 @@ HIP_SOURCES = [
     "awq_tiled_gemm.hip",
     "int8_gemm.hip",
     "int8_tiled_gemm.hip",
+    "fp8_tiled_gemm.hip",
     "prefill_attention.hip",
     "prepare_inputs.hip",
     "fp8_quant.hip",

@@ -80,6 +80,12 @@ extern "C" int lvllm_set_tuning(const char* key, int value) {
   } else if (k == "w4_tiled_max_rows") {
     LV_CHECK(value >= 0, "w4_tiled_max_rows must be non-negative (0: never)");
     lvllm::tuning().w4_tiled_max_rows = value;
+  } else if (k == "fp8_tiled_min_rows") {
+    LV_CHECK(value >= 1, "fp8_tiled_min_rows must be positive (above fp8_tiled_max_rows: never)");
+    lvllm::tuning().fp8_tiled_min_rows = value;
+  } else if (k == "fp8_tiled_max_rows") {
+    LV_CHECK(value >= 0, "fp8_tiled_max_rows must be non-negative (0: never)");
+    lvllm::tuning().fp8_tiled_max_rows = value;
   } else {
     LV_CHECK(false, "unknown tuning key '" + k + "'");
   }
@@ -108,6 +114,8 @@ extern "C" int lvllm_get_tuning(const char* key, int* value) {
   else if (k == "int8_tiled_min_rows") *value = t.int8_tiled_min_rows;
   else if (k == "w4_tiled_min_rows") *value = t.w4_tiled_min_rows;
   else if (k == "w4_tiled_max_rows") *value = t.w4_tiled_max_rows;
+  else if (k == "fp8_tiled_min_rows") *value = t.fp8_tiled_min_rows;
+  else if (k == "fp8_tiled_max_rows") *value = t.fp8_tiled_max_rows;
   else LV_CHECK(false, "unknown tuning key '" + k + "'");
   return 0;
 }

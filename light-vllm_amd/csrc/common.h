@@ -30,6 +30,7 @@ void set_error(const std::string& msg);
 //   varlen_dense     see Tuning
 //   int8_tiled_min_rows    see Tuning
 //   w4_tiled_min_rows, w4_tiled_max_rows    see Tuning
+//   fp8_tiled_min_rows, fp8_tiled_max_rows  see Tuning
 struct Tuning {
   int gemm_workgroups = 256;
   int gemm_workgroups_wide = 0;  // for projections with >= gemm_wide_min_tiles n-tiles; 0 = as above
@@ -65,6 +66,13 @@ struct Tuning {
                                 // packed weight and call the library GEMM.  Measured (profiles/awq_tiled_gemm.md): faster
                                 // beyond the spread on all four 8B projections at 65 .. 512 rows, slower on two at 1024;
                                 // min_rows huge = never the tiled kernel
+  int fp8_tiled_min_rows = 65;  // W8A8 fp8 linear above the streaming kernel's 64 rows (quantization/fp8.py): calls with
+  int fp8_tiled_max_rows = 0;   // min_rows <= M <= max_rows quantise without padding and take the LDS-tiled kernel
+                                // (fp8_tiled_gemm.hip), the others go through torch._scaled_mm.  min above max = never,
+                                // the default: with per-tensor scales (the engine's mode) the library route wins on
+                                // gate_up at every measured M and on all four 8B projections from 512 rows on; with
+                                // per-token x per-channel scales the tiled route wins on all four at 65 .. 2048 rows,
+                                // set (65, 2048) there (profiles/fp8_tiled_gemm.md)
 };
 Tuning& tuning();
 

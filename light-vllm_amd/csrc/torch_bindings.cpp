@@ -1377,18 +1377,95 @@ torch::Tensor linear_w8a8_int8_tiled(const torch::Tensor& x_q, const torch::Tens
   return y;
 }
 
-// The reference's operator for int8 operands: a [M, K] row-major, b [K, N] with strides (1, K) (weight.t()), fp32
-// a_scales (1 or M) and b_scales (1 or N).  Inside the kernel's envelope b is packed on every call -- correct, not
-// fast; a host that keeps its weights calls int8_pack once and skinny_linear_w8a8_int8 per step.  Outside it (K % 64
-// or N % 16) the accumulators come from a float64 matmul of the integer operands, which is exact, and the same
-// epilogue is applied in fp32.
+bool fp8_tiled_shape_ok(int64_t N, int64_t K) {
+  return N > 0 && K > 0 && N % 16 == 0 && K % 64 == 0 && N * K < ((int64_t)1 << 32) - 16;
+}
+
+// y [M, N] (contiguous, bf16 / f16) = (x_fp8 . W8^T)[m, n] * sx[m] * sw[n] (+ bias) from the packed fp8 weight on the
+// LDS-tiled kernel; x_scale has 1 or M elements, w_scale 1 or N
+void fp8_linear_into(torch::Tensor& y, const torch::Tensor& x_in, const torch::Tensor& w_packed,
+                     const torch::Tensor& x_scale, const torch::Tensor& w_scale, int64_t N, int64_t K,
+                     const std::optional<torch::Tensor>& bias, const char* op) {
+  LV_CHECK_DEVICE(x_in);
+  LV_CHECK_DEVICE(w_packed);
+  TORCH_CHECK(x_in.dim() == 2 && x_in.size(1) == K && x_in.scalar_type() == at::kFloat8_e4m3fn, op,
+              ": x_fp8 must be [M, K] float8_e4m3fn");
+  TORCH_CHECK(fp8_tiled_shape_ok(N, K), op, ": N % 16 == 0, K % 64 == 0, N * K < 2^32 - 16");
+  TORCH_CHECK(w_packed.is_contiguous() && w_packed.element_size() == 1 && w_packed.numel() == N * K, op,
+              ": w_packed does not have the size pack_fp8_weight gives for this N, K");
+  TORCH_CHECK(y.scalar_type() == at::kHalf || y.scalar_type() == at::kBFloat16, op, ": the output is f16 or bf16");
+  TORCH_CHECK(!bias || (bias->is_cuda() && bias->is_contiguous() && bias->numel() == N &&
+                        bias->scalar_type() == y.scalar_type()),
+              op, ": bias must be [N] of the output's dtype");
+  const int64_t M = x_in.size(0);
+  if (M == 0) return;
+  auto scale = [&](const torch::Tensor& s, int64_t n, const char* what) {
+    TORCH_CHECK(s.is_cuda() && s.scalar_type() == at::kFloat && (s.numel() == 1 || s.numel() == n), op, ": ", what,
+                " must be fp32 on the GPU with one element or one per row / channel");
+    return s.reshape({-1}).contiguous();
+  };
+  const auto sx = scale(x_scale, M, "x_scale"), sw = scale(w_scale, N, "w_scale");
+  const bool strided_ok = x_in.stride(1) == 1 && x_in.stride(0) >= K && x_in.stride(0) % 16 == 0 &&
+                          ((uintptr_t)x_in.data_ptr() & 15) == 0;
+  const torch::Tensor x = strided_ok ? x_in : x_in.contiguous();
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(device_of(x));
+  TORCH_CHECK(M < ((int64_t)1 << 31) && (M - 1) * x.stride(0) + K < ((int64_t)1 << 31), op, ": x_fp8 spans 2 GiB or more");
+  const int64_t ws_bytes = lvllm_gemm_w8a8_fp8_workspace_bytes((int)M, (int)N, (int)K);
+  torch::Tensor ws;
+  if (ws_bytes > 0) ws = torch::empty({ws_bytes / 4}, x.options().dtype(torch::kFloat));
+  check(lvllm_gemm_w8a8_fp8(y.data_ptr(), x.data_ptr(), w_packed.data_ptr(), sx.data_ptr<float>(), sw.data_ptr<float>(),
+                            (int)sx.numel(), (int)sw.numel(), bias ? bias->data_ptr() : nullptr, (int)M, (int)N, (int)K,
+                            x.stride(0), y.scalar_type() == at::kBFloat16 ? LVLLM_BF16 : LVLLM_F16,
+                            ws_bytes > 0 ? ws.data_ptr() : nullptr, ws_bytes, current_stream(x)));
+}
+
+// the LDS-tiled W8A8 fp8 kernel at any M on activations that are already fp8 (ops.scaled_fp8_quant)
+torch::Tensor linear_w8a8_fp8_tiled(const torch::Tensor& x_fp8, const torch::Tensor& w_packed,
+                                    const torch::Tensor& x_scale, const torch::Tensor& w_scale, int64_t N, int64_t K,
+                                    const std::optional<torch::Tensor>& bias, at::ScalarType out_dtype) {
+  LV_CHECK_DEVICE(x_fp8);
+  TORCH_CHECK(x_fp8.dim() == 2, "linear_w8a8_fp8_tiled: x_fp8 must be [M, K] float8_e4m3fn");
+  auto y = torch::empty({x_fp8.size(0), N}, x_fp8.options().dtype(out_dtype));
+  fp8_linear_into(y, x_fp8, w_packed, x_scale, w_scale, N, K, bias, "linear_w8a8_fp8_tiled");
+  return y;
+}
+
+// cutlass_scaled_mm on fp8 operands.  Inside the tiled kernel's envelope b.t() is packed on every call (correct, not
+// fast); outside it the product of the fp8 values is formed in float64 and the kernel's epilogue applied in fp32.
+void cutlass_scaled_mm_fp8(torch::Tensor& out, const torch::Tensor& a, const torch::Tensor& b,
+                           const torch::Tensor& a_scales, const torch::Tensor& b_scales,
+                           const std::optional<torch::Tensor>& bias, int64_t M, int64_t N, int64_t K) {
+  if (fp8_tiled_shape_ok(N, K) && (M - 1) * std::max<int64_t>(a.stride(0), K) + K < ((int64_t)1 << 31)) {
+    const auto w = b.t().contiguous().view(at::kByte);  // [N, K]
+    const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(device_of(w));
+    auto packed = torch::empty_like(w);
+    check(lvllm_pack_weight(packed.data_ptr(), w.data_ptr(), (int)N, (int)(K / 2), LVLLM_F16, current_stream(w)));
+    fp8_linear_into(out, a, packed, a_scales, b_scales, N, K,
+                    bias ? std::optional<torch::Tensor>(bias->contiguous()) : std::nullopt, "cutlass_scaled_mm");
+    return;
+  }
+  TORCH_CHECK(a_scales.scalar_type() == at::kFloat && (a_scales.numel() == 1 || a_scales.numel() == M) &&
+                  b_scales.scalar_type() == at::kFloat && (b_scales.numel() == 1 || b_scales.numel() == N),
+              "cutlass_scaled_mm: a_scales (1 or M) and b_scales (1 or N) must be fp32");
+  const auto acc = at::matmul(a.to(at::kFloat).to(at::kDouble), b.to(at::kFloat).to(at::kDouble)).to(at::kFloat);
+  auto r = (acc * a_scales.reshape({-1, 1})) * b_scales.reshape({1, -1});
+  if (bias) r = r + bias->to(at::kFloat).unsqueeze(0);
+  out.copy_(r);
+}
+
+// The reference's operator: a [M, K] row-major, b [K, N] with strides (1, K) (weight.t()), both int8 or both
+// float8_e4m3fn, fp32 a_scales (1 or M) and b_scales (1 or N).  Inside the kernel's envelope b is packed on every call
+// -- correct, not fast; a host that keeps its weights calls int8_pack once and skinny_linear_w8a8_int8 per step.
+// Outside it (K % 64 or N % 16) the accumulators come from a float64 matmul of the integer operands, which is exact,
+// and the same epilogue is applied in fp32.  fp8 operands: cutlass_scaled_mm_fp8.
 void cutlass_scaled_mm(torch::Tensor& out, const torch::Tensor& a, const torch::Tensor& b, const torch::Tensor& a_scales,
                        const torch::Tensor& b_scales, const std::optional<torch::Tensor>& bias) {
   LV_CHECK_DEVICE(a);
   LV_CHECK_DEVICE(b);
   LV_CHECK_DEVICE(out);
-  TORCH_CHECK(a.scalar_type() == at::kChar && b.scalar_type() == at::kChar,
-              "cutlass_scaled_mm: only int8 a / b are served here (fp8 goes through apply_fp8_linear)");
+  const bool fp8 = a.scalar_type() == at::kFloat8_e4m3fn && b.scalar_type() == at::kFloat8_e4m3fn;
+  TORCH_CHECK(fp8 || (a.scalar_type() == at::kChar && b.scalar_type() == at::kChar),
+              "cutlass_scaled_mm: a / b are both int8 or both float8_e4m3fn");
   TORCH_CHECK(a.dim() == 2 && b.dim() == 2 && out.dim() == 2 && a.size(1) == b.size(0) && out.size(0) == a.size(0) &&
                   out.size(1) == b.size(1),
               "cutlass_scaled_mm: a [M, K], b [K, N], out [M, N]");
@@ -1400,6 +1477,7 @@ void cutlass_scaled_mm(torch::Tensor& out, const torch::Tensor& a, const torch::
   TORCH_CHECK(!bias || (bias->is_cuda() && bias->numel() == N && bias->scalar_type() == out.scalar_type()),
               "cutlass_scaled_mm: bias must be [N] of out's dtype");
   if (M == 0 || N == 0) return;
+  if (fp8) return cutlass_scaled_mm_fp8(out, a, b, a_scales, b_scales, bias, M, N, K);
   const auto w_q = b.t();  // [N, K]
   if (K > 0 && K % 64 == 0 && N % 16 == 0 && K < 131072) {
     int8_linear_into(out, a, int8_pack(w_q.contiguous()), a_scales, b_scales, N, K,
@@ -1557,6 +1635,10 @@ TORCH_LIBRARY(_C_amd, amd) {
   amd.def("linear_w8a8_int8_tiled(Tensor x_q, Tensor w_packed, Tensor x_scale, Tensor w_scale, int N, int K, "
           "Tensor? bias, ScalarType out_dtype) -> Tensor");
   amd.impl("linear_w8a8_int8_tiled", torch::kCUDA, &linear_w8a8_int8_tiled);
+  // W8A8 fp8 for prefill batches: activations already fp8 (scaled_fp8_quant), the decode kernel's packed weight
+  amd.def("linear_w8a8_fp8_tiled(Tensor x_fp8, Tensor w_packed, Tensor x_scale, Tensor w_scale, int N, int K, "
+          "Tensor? bias, ScalarType out_dtype) -> Tensor");
+  amd.impl("linear_w8a8_fp8_tiled", torch::kCUDA, &linear_w8a8_fp8_tiled);
   amd.def("gelu(Tensor! out, Tensor x) -> ()");
   amd.impl("gelu", torch::kCUDA, &gelu);
   amd.def("add_layer_norm(Tensor! out, Tensor x, Tensor? y, Tensor weight, Tensor bias, float epsilon) -> ()");

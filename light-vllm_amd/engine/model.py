@@ -101,7 +101,7 @@ def linear(x: torch.Tensor, w: "Weight", bias: Optional[torch.Tensor] = None) ->
         if x.shape[0] <= 64 and w.w8_packed is not None:
             return torch.ops._C_amd.skinny_linear_w8a8(x, w.w8_packed, w.w_scale, w.x_scale, w.N, w.K, bias)
         from ..quantization import apply_fp8_linear
-        return apply_fp8_linear(x, w.w8_t, w.w_scale, input_scale=w.x_scale, bias=bias)
+        return apply_fp8_linear(x, w.w8_t, w.w_scale, input_scale=w.x_scale, bias=bias, w_packed=w.w8_packed)
     if w.w4_packed is not None:  # W4A16: skinny_linear_w4a16 routes (streaming kernel <= 64 rows, LDS-tiled kernel for prefill)
         from ..quantization import apply_awq_linear
         return apply_awq_linear(x, w.w4_packed, w.w4_meta, *w.awq, bias=bias)

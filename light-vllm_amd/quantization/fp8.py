@@ -20,9 +20,22 @@ def per_tensor_quantize_weight(weight: torch.Tensor) -> Tuple[torch.Tensor, torc
 def apply_fp8_linear(input: torch.Tensor, weight: torch.Tensor, weight_scale: torch.Tensor,
                      input_scale: Optional[torch.Tensor] = None, input_scale_ub: Optional[torch.Tensor] = None,
                      bias: Optional[torch.Tensor] = None, cutlass_fp8_supported: bool = False,
-                     use_per_token_if_dynamic: bool = False) -> torch.Tensor:
+                     use_per_token_if_dynamic: bool = False, w_packed: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """With `w_packed` (pack_fp8_weight of the same weight), a row count within tuning fp8_tiled_min_rows ..
+    fp8_tiled_max_rows and a shape inside the kernel's envelope: quantise without padding and run the LDS-tiled
+    kernel with both scales in its epilogue.  Every other call goes through torch._scaled_mm as in the reference."""
     if cutlass_fp8_supported:
         raise NotImplementedError("cutlass_scaled_mm is an NVIDIA kernel; use the torch._scaled_mm path")
+    if w_packed is not None and input.is_cuda:
+        M, (K, N) = input.shape[0], weight.shape
+        get = torch.ops._C_amd.get_tuning
+        if (get("fp8_tiled_min_rows") <= M <= get("fp8_tiled_max_rows") and N % 16 == 0 and K % 64 == 0
+                and N * K < (1 << 32) - 16 and M * K < (1 << 31)):
+            qinput, x_scale = ops.scaled_fp8_quant(input.contiguous(), input_scale,
+                                                   scale_ub=input_scale_ub if use_per_token_if_dynamic else None,
+                                                   use_per_token_if_dynamic=use_per_token_if_dynamic)
+            return torch.ops._C_amd.linear_w8a8_fp8_tiled(qinput, w_packed, x_scale, weight_scale, N, K, bias,
+                                                          input.dtype)
     # the input is padded to 17 rows as in the reference (w8a8_utils.py:137-144)
     qinput, x_scale = ops.scaled_fp8_quant(input, input_scale, num_token_padding=17,
                                            scale_ub=input_scale_ub if use_per_token_if_dynamic else None,

@@ -311,6 +311,88 @@ def awq_prefill_leg(out_path):
             f.write("\n".join(lines) + "\n")
 
 
+def fp8_prefill_leg(out_path):
+    """--fp8-prefill [out.md]: the W8A8 fp8 linear from bf16 activations, (a) the new route of apply_fp8_linear
+    (scaled_fp8_quant without padding + the LDS-tiled kernel, linear_w8a8_fp8_tiled, scales in the epilogue) against
+    (b) the route it had before (scaled_fp8_quant padded to 17 rows + torch._scaled_mm, plus the three elementwise
+    passes in per-token mode), and (c) the tiled kernel alone on activations quantised beforehand.  Two scale modes:
+    static per-tensor x per-tensor (the engine's) and dynamic per-token x per-channel.  The method of --int8-prefill:
+    same process, weights rotate through > 0.5 GB per format, 3 warm-up rounds, then REGIONS regions of PER rounds, the
+    legs alternating launch by launch inside a round; a region's figure is the median of its device-event times and
+    every region is listed.  The tuning keys are set once, outside the timed spans.  Before timing, each row asserts
+    the two routes within two bf16 ulps at the output's scale of each other."""
+    from light_vllm_amd.quantization import apply_fp8_linear, pack_fp8_weight
+    REGIONS = 5
+    shapes = [("qkv", 6144, 4096), ("o", 4096, 4096), ("gate_up", 28672, 4096), ("down", 4096, 14336)]
+    fmt = lambda r: " ".join(f"{t:.0f}" for t in r)  # noqa: E731
+    med = lambda r: sorted(r)[len(r) // 2]  # noqa: E731
+    get, put = torch.ops._C_amd.get_tuning, torch.ops._C_amd.set_tuning
+    default = get("fp8_tiled_min_rows"), get("fp8_tiled_max_rows")
+    lines = ["| scales | shape | M | quantise + tiled us (regions) | quantise + _scaled_mm us (regions) | tiled alone us "
+             "(regions) | new route Tflop/s | _scaled_mm route Tflop/s | tiled alone Tflop/s | new vs _scaled_mm route |",
+             "|---|---|---|---|---|---|---|---|---|---|"]
+    put("fp8_tiled_min_rows", 1)  # with w_packed: always the tiled kernel; without: always the library
+    put("fp8_tiled_max_rows", 1 << 30)
+    for name, N, K in shapes:
+        w8 = torch.randint(0, 120, (N, K), device=dev, dtype=torch.uint8).view(torch.float8_e4m3fn)  # finite values
+        n8 = int(0.55e9 // (N * K)) + 1
+        wts = [w8.clone().t() for _ in range(n8)]
+        wps = [pack_fp8_weight(w.t()) for w in wts]
+        for mode in ("per-tensor", "per-token x per-channel"):
+            per_token = mode != "per-tensor"
+            ws = torch.rand(N, 1, device=dev) * 1e-3 + 1e-4 if per_token else torch.full((1,), 5e-4, device=dev)
+            xs = None if per_token else torch.full((1,), 0.01, device=dev)
+            for M in (65, 128, 256, 512, 1024, 2048, 8192):
+                PER = 20 if M <= 512 else 6
+                x = (torch.randn(M, K, device=dev) * 0.5).to(torch.bfloat16)
+                xq, sx = _custom_ops.scaled_fp8_quant(x, xs, use_per_token_if_dynamic=per_token)
+                fs = [lambda i: apply_fp8_linear(x, wts[i % n8], ws, input_scale=xs, use_per_token_if_dynamic=per_token,
+                                                 w_packed=wps[i % n8]),
+                      lambda i: apply_fp8_linear(x, wts[i % n8], ws, input_scale=xs, use_per_token_if_dynamic=per_token),
+                      lambda i: torch.ops._C_amd.linear_w8a8_fp8_tiled(xq, wps[i % n8], sx, ws, N, K, None, torch.bfloat16)]
+                yn, yl = fs[0](0).float(), fs[1](0).float()
+                assert torch.equal(fs[0](0), fs[2](0))
+                assert (yn - yl).abs().max().item() <= 2 ** -7 * yl.abs().max().item(), (name, mode, M)
+                del yn, yl
+                for i in range(3):
+                    for f in fs:
+                        f(i)
+                torch.cuda.synchronize()
+                regions, it = [[] for _ in fs], 0
+                for _ in range(REGIONS):
+                    evs = []
+                    for _ in range(PER):
+                        e = [torch.cuda.Event(enable_timing=True) for _ in range(len(fs) + 1)]
+                        e[0].record()
+                        for j, f in enumerate(fs):
+                            f(it)
+                            e[j + 1].record()
+                        evs.append(e)
+                        it += 1
+                    torch.cuda.synchronize()
+                    for j in range(len(fs)):
+                        regions[j].append(med([e[j].elapsed_time(e[j + 1]) * 1e3 for e in evs]))
+                rn, rl, rk = regions
+                flop = 2.0 * M * N * K
+                verdict = ("faster beyond the spread" if max(rn) < min(rl) else
+                           "SLOWER beyond the spread" if min(rn) > max(rl) else "within the spread")
+                lines.append(f"| {mode} | {name} {N}x{K} | {M} | {med(rn):.1f} ({fmt(rn)}) | {med(rl):.1f} ({fmt(rl)}) | "
+                             f"{med(rk):.1f} ({fmt(rk)}) | {flop / med(rn) / 1e6:.0f} | {flop / med(rl) / 1e6:.0f} | "
+                             f"{flop / med(rk) / 1e6:.0f} | {med(rl) / med(rn):.2f}x, {verdict} |")
+                print(lines[-1], flush=True)
+        del wts, wps
+        torch.cuda.empty_cache()
+    put("fp8_tiled_min_rows", default[0])
+    put("fp8_tiled_max_rows", default[1])
+    if out_path:
+        with open(out_path, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if len(sys.argv) > 1 and sys.argv[1] == "--fp8-prefill":
+    fp8_prefill_leg(sys.argv[2] if len(sys.argv) > 2 else None)
+    sys.exit(0)
+
 if len(sys.argv) > 1 and sys.argv[1] == "--awq-prefill":
     awq_prefill_leg(sys.argv[2] if len(sys.argv) > 2 else None)
     sys.exit(0)
