@@ -646,6 +646,28 @@ int lvllm_gemm_w8a8_int8(void* y, const void* x_q, const void* w_packed, const f
                          const void* bias, int M, int N, int K, int64_t ldx, int dtype, void* workspace,
                          int64_t workspace_bytes, void* stream);
 
+/* ---- W4A8 MXFP4: OCP microscaling e2m1 weights, fp8 e4m3fn activations (csrc/mxfp4_gemm.hip) -------------------
+ * Checkpoint tensors: codes uint8 [N, K/2] (element k in byte k/2, even k in the low nibble; e2m1 = sign and the
+ * magnitudes 0, 0.5, 1, 1.5, 2, 3, 4, 6), scales uint8 [N, K/32] (E8M0: 2^(e - 127) for 32 consecutive k of a row;
+ * 0xFF is NaN and outside the contract).  N % 16 == 0, K % 128 == 0, K < 131072.
+ * lvllm_mxfp4_pack: once, after loading -- w_packed = lvllm_mxfp4_packed_bytes(N, K) bytes, [N/16][K/128][lane 64][16
+ * bytes]; e_packed = lvllm_mxfp4_scale_bytes(N, K) bytes, [N/16][ceil(K/512)][lane 64][4 bytes], k-steps past K with
+ * scale 127.  It waits for the stream and returns 1 if a scale byte is 0xFF; 3 outside the envelope (the two size
+ * queries return 0 there).
+ * lvllm_skinny_gemm_w4a8_mxfp4: y [M, N] = T(x_scale[m] * sum_k x[m, k] * W4[n, k] * 2^(E[n, k/32] - 127) + bias[n]),
+ * fp32 accumulation in the scaled MFMA, the scale and the bias applied in fp32 in that order, one rounding to T = bf16
+ * / f16; x_fp8 [M <= 64, K] e4m3fn (rows ldx BYTES apart, ldx % 16 == 0, 16-byte aligned), x_scale fp32 [M], bias [N]
+ * of T or null.  Returns 3 and launches nothing outside the envelope.  workspace: fp32 split-K partials,
+ * lvllm_skinny_gemm_w4a8_mxfp4_workspace_bytes(M, N, K) bytes (0 up to K = 4096), 16-byte aligned. */
+int64_t lvllm_mxfp4_packed_bytes(int N, int K);
+int64_t lvllm_mxfp4_scale_bytes(int N, int K);
+int lvllm_mxfp4_pack(void* w_packed, void* e_packed, const void* codes, const void* scales, int N, int K,
+                     void* stream);
+int64_t lvllm_skinny_gemm_w4a8_mxfp4_workspace_bytes(int M, int N, int K);
+int lvllm_skinny_gemm_w4a8_mxfp4(void* y, const void* x_fp8, const void* w_packed, const void* e_packed,
+                                 const float* x_scale, const void* bias, int M, int N, int K, int64_t ldx, int dtype,
+                                 void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- device queries (csrc/cuda_utils.h, torch_bindings.cpp:271-279) ------- */
 int64_t lvllm_get_device_attribute(int64_t attribute, int64_t device_id);
 int64_t lvllm_get_max_shared_memory_per_block_device_attribute(int64_t device_id);

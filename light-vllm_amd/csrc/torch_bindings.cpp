@@ -1491,6 +1491,67 @@ void cutlass_scaled_mm(torch::Tensor& out, const torch::Tensor& a, const torch::
   out.copy_(r);
 }
 
+// ---- W4A8 MXFP4 (csrc/mxfp4_gemm.hip): OCP e2m1 codes [N, K/2] and E8M0 scales [N, K/32], both uint8
+std::tuple<torch::Tensor, torch::Tensor> mxfp4_pack(const torch::Tensor& codes, const torch::Tensor& scales) {
+  LV_CHECK_DEVICE(codes);
+  LV_CHECK_DEVICE(scales);
+  TORCH_CHECK(codes.dim() == 2 && scales.dim() == 2 && codes.is_contiguous() && scales.is_contiguous() &&
+                  codes.scalar_type() == at::kByte && scales.scalar_type() == at::kByte,
+              "mxfp4_pack: contiguous uint8 codes [N, K/2] and scales [N, K/32]");
+  const int64_t N = codes.size(0), K = codes.size(1) * 2;
+  TORCH_CHECK(N < ((int64_t)1 << 31) && K < 131072 && lvllm_mxfp4_packed_bytes((int)N, (int)K) > 0,
+              "mxfp4_pack: N % 16 == 0, K % 128 == 0, K < 131072");
+  TORCH_CHECK(scales.size(0) == N && scales.size(1) * 32 == K, "mxfp4_pack: scales must be [N, K/32]");
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(device_of(codes));
+  auto w = torch::empty({lvllm_mxfp4_packed_bytes((int)N, (int)K)}, codes.options());
+  auto e = torch::empty({lvllm_mxfp4_scale_bytes((int)N, (int)K)}, codes.options());
+  check(lvllm_mxfp4_pack(w.data_ptr(), e.data_ptr(), codes.data_ptr(), scales.data_ptr(), (int)N, (int)K,
+                         current_stream(codes)));
+  return {w, e};
+}
+
+// y [M, N] = T(sx[m] * (x_fp8 . W^T)[m, n] + bias[n]) from the packed pair, any M >= 1: above 64 rows the same kernel
+// runs over chunks of 64 rows (row for row the <= 64 result; the weights stream once per chunk).
+torch::Tensor skinny_linear_w4a8_mxfp4(const torch::Tensor& x_in, const torch::Tensor& w_packed,
+                                       const torch::Tensor& e_packed, const torch::Tensor& x_scale, int64_t N, int64_t K,
+                                       const std::optional<torch::Tensor>& bias, at::ScalarType out_dtype) {
+  const char* op = "skinny_linear_w4a8_mxfp4";
+  LV_CHECK_DEVICE(x_in);
+  LV_CHECK_DEVICE(w_packed);
+  LV_CHECK_DEVICE(e_packed);
+  TORCH_CHECK(x_in.dim() == 2 && x_in.size(1) == K && x_in.scalar_type() == at::kFloat8_e4m3fn, op,
+              ": x_fp8 must be [M, K] float8_e4m3fn");
+  TORCH_CHECK(N > 0 && K > 0 && N < ((int64_t)1 << 31) && K < 131072 && lvllm_mxfp4_packed_bytes((int)N, (int)K) > 0, op,
+              ": N % 16 == 0, K % 128 == 0, K < 131072");
+  TORCH_CHECK(w_packed.is_contiguous() && e_packed.is_contiguous() && w_packed.element_size() == 1 &&
+                  e_packed.element_size() == 1 && w_packed.numel() == lvllm_mxfp4_packed_bytes((int)N, (int)K) &&
+                  e_packed.numel() == lvllm_mxfp4_scale_bytes((int)N, (int)K),
+              op, ": w_packed / e_packed do not have the sizes mxfp4_pack gives for this N, K");
+  TORCH_CHECK(out_dtype == at::kHalf || out_dtype == at::kBFloat16, op, ": the output is f16 or bf16");
+  TORCH_CHECK(!bias || (bias->is_cuda() && bias->is_contiguous() && bias->numel() == N && bias->scalar_type() == out_dtype),
+              op, ": bias must be [N] of the output's dtype");
+  const int64_t M = x_in.size(0);
+  auto y = torch::empty({M, N}, x_in.options().dtype(out_dtype));
+  if (M == 0) return y;
+  const auto sx = int8_scale_vector(x_scale, M, "x_scale");
+  const bool strided_ok = x_in.stride(1) == 1 && x_in.stride(0) >= K && x_in.stride(0) % 16 == 0 &&
+                          ((uintptr_t)x_in.data_ptr() & 15) == 0;
+  const torch::Tensor x = strided_ok ? x_in : x_in.contiguous();
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(device_of(x));
+  const int64_t ws_bytes = lvllm_skinny_gemm_w4a8_mxfp4_workspace_bytes((int)std::min<int64_t>(M, 64), (int)N, (int)K);
+  torch::Tensor ws;
+  if (ws_bytes > 0) ws = torch::empty({ws_bytes / 4}, x.options().dtype(torch::kFloat));
+  const int dt = out_dtype == at::kBFloat16 ? LVLLM_BF16 : LVLLM_F16;
+  for (int64_t m0 = 0; m0 < M; m0 += 64) {
+    const int64_t rows = std::min<int64_t>(64, M - m0);
+    check(lvllm_skinny_gemm_w4a8_mxfp4((char*)y.data_ptr() + m0 * N * 2, (const char*)x.data_ptr() + m0 * x.stride(0),
+                                       w_packed.data_ptr(), e_packed.data_ptr(), sx.data_ptr<float>() + m0,
+                                       bias ? bias->data_ptr() : nullptr, (int)rows, (int)N, (int)K, x.stride(0), dt,
+                                       ws_bytes > 0 ? ws.data_ptr() : nullptr, ws_bytes, current_stream(x)));
+  }
+  return y;
+}
+
 int64_t get_device_attribute(int64_t attribute, int64_t device_id) {
   return lvllm_get_device_attribute(attribute, device_id);
 }
@@ -1635,6 +1696,12 @@ TORCH_LIBRARY(_C_amd, amd) {
   amd.def("linear_w8a8_int8_tiled(Tensor x_q, Tensor w_packed, Tensor x_scale, Tensor w_scale, int N, int K, "
           "Tensor? bias, ScalarType out_dtype) -> Tensor");
   amd.impl("linear_w8a8_int8_tiled", torch::kCUDA, &linear_w8a8_int8_tiled);
+  // W4A8 MXFP4: pack the checkpoint's codes and block scales once, then stream them with fp8 activations
+  amd.def("mxfp4_pack(Tensor codes, Tensor scales) -> (Tensor, Tensor)");
+  amd.impl("mxfp4_pack", torch::kCUDA, &mxfp4_pack);
+  amd.def("skinny_linear_w4a8_mxfp4(Tensor x_fp8, Tensor w_packed, Tensor e_packed, Tensor x_scale, int N, int K, "
+          "Tensor? bias, ScalarType out_dtype) -> Tensor");
+  amd.impl("skinny_linear_w4a8_mxfp4", torch::kCUDA, &skinny_linear_w4a8_mxfp4);
   // W8A8 fp8 for prefill batches: activations already fp8 (scaled_fp8_quant), the decode kernel's packed weight
   amd.def("linear_w8a8_fp8_tiled(Tensor x_fp8, Tensor w_packed, Tensor x_scale, Tensor w_scale, int N, int K, "
           "Tensor? bias, ScalarType out_dtype) -> Tensor");

@@ -42,6 +42,8 @@ class ModelConfig:
     # lm_head stays 16-bit, as AWQ checkpoints keep it
     # "int8": W8A8 int8 projections (per-channel weight scales, dynamic per-token activation scales, int32
     # accumulation); the lm_head stays 16-bit
+    # "mxfp4": W4A8 projections (OCP MXFP4 weights: e2m1 with one E8M0 scale per 32 input channels; dynamic per-token
+    # fp8 activations; the gfx950 scaled MFMA); the lm_head stays 16-bit
     quantization: Optional[str] = None
     awq_group_size: int = 128
     # W8A8 decode steps: activations quantised once by their producer (norm launches, SwiGLU epilogue) and handed to

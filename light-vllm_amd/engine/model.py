@@ -23,7 +23,7 @@ class Weight:
     Twice the bytes; sized for 288 GB of HBM."""
 
     __slots__ = ("w", "packed", "N", "K", "w8_t", "w8_packed", "w_scale", "x_scale", "x_absmax", "awq", "w4_packed",
-                 "w4_meta", "i8", "i8_packed", "i8_scale")
+                 "w4_meta", "i8", "i8_packed", "i8_scale", "mx4", "mx4_packed", "mx4_scale")
 
     def __init__(self, w: torch.Tensor, pack: bool = True):
         self.w = w
@@ -34,6 +34,8 @@ class Weight:
         self.x_absmax = None  # calibration: running max |x| of this projection's input
         self.awq = self.w4_packed = self.w4_meta = None  # W4A16: (qweight, qzeros, scales) and their packed pair
         self.i8 = self.i8_packed = self.i8_scale = None  # W8A8 int8: row-major OR packed weight, per-channel scales
+        # W4A8 MXFP4: row-major OR packed e2m1 codes, and the E8M0 block scales in the same order as the codes
+        self.mx4 = self.mx4_packed = self.mx4_scale = None
 
     def numel(self) -> int:
         return self.N * self.K
@@ -44,6 +46,8 @@ class Weight:
             return sum(t.numel() * t.element_size() for t in self.awq)
         if self.i8_scale is not None:
             return self.numel() + self.i8_scale.numel() * self.i8_scale.element_size()
+        if self.mx4_scale is not None:
+            return self.numel() // 2 + self.numel() // 32
         return self.numel() * (1 if self.w8_t is not None else self.w.element_size())
 
     @staticmethod
@@ -79,6 +83,23 @@ class Weight:
             self.i8 = q
         self.w = self.packed = None
 
+    @staticmethod
+    def mxfp4_ok(N: int, K: int) -> bool:
+        """The envelope of the W4A8 MXFP4 streaming kernel (lvllm_skinny_gemm_w4a8_mxfp4)."""
+        return N % 16 == 0 and K % 128 == 0 and K < 131072 and N * K // 2 < (1 << 32) - 16
+
+    def quantize_mxfp4(self) -> None:
+        """OCP MXFP4 weights (quantization/mxfp4.py: e2m1 codes, one E8M0 scale per 32 input channels; K % 32 == 0);
+        the 16-bit copies are dropped.  Inside the kernel's envelope only the packed pair is kept, otherwise the
+        checkpoint-order pair for the dequantising fallback."""
+        from ..quantization import pack_mxfp4_weight, quantize_mxfp4_weight
+        codes, scales = quantize_mxfp4_weight(self.w)
+        if self.mxfp4_ok(self.N, self.K):
+            self.mx4_packed, self.mx4_scale = pack_mxfp4_weight(codes, scales)
+        else:
+            self.mx4, self.mx4_scale = codes, scales
+        self.w = self.packed = None
+
     def quantize_fp8(self) -> None:
         """Per-tensor e4m3 weights + the calibrated static activation scale; the 16-bit copies are
         dropped (fp8.py:196-239 of the reference quantises at load time the same way)."""
@@ -108,6 +129,10 @@ def linear(x: torch.Tensor, w: "Weight", bias: Optional[torch.Tensor] = None) ->
     if w.i8_scale is not None:  # W8A8 int8: dynamic per-token activation scales, then the int32 streaming kernel
         from ..quantization import apply_int8_linear
         return apply_int8_linear(x, w.i8_packed if w.i8_packed is not None else w.i8.t(), w.i8_scale, bias=bias)
+    if w.mx4_scale is not None:  # W4A8 MXFP4: dynamic per-token fp8 activations, then the scaled-MFMA streaming kernel
+        from ..quantization import apply_mxfp4_linear
+        return apply_mxfp4_linear(x, w.mx4_packed if w.mx4_packed is not None else w.mx4, w.mx4_scale, w.N, w.K,
+                                  bias=bias)
     if _CALIBRATING:
         m = x.detach().abs().amax()
         w.x_absmax = m if w.x_absmax is None else torch.maximum(w.x_absmax, m)
@@ -191,6 +216,15 @@ class DecoderModel:
                 for w in (l.qkv, l.o, l.gate_up, l.down):
                     if w.w.is_cuda:
                         w.quantize_int8()
+            torch.cuda.empty_cache()
+        elif cfg.quantization == "mxfp4":
+            # the four projections of every layer; activations are quantised to fp8 per token in front of each of
+            # them (dynamic_per_token_scaled_fp8_quant), the lm_head stays 16-bit, and so does a projection whose K
+            # is no multiple of the MX block
+            for l in self.layers:
+                for w in (l.qkv, l.o, l.gate_up, l.down):
+                    if w.w.is_cuda and w.K % 32 == 0:
+                        w.quantize_mxfp4()
             torch.cuda.empty_cache()
         elif cfg.quantization is not None:
             raise ValueError(f"unsupported quantization {cfg.quantization!r}")

@@ -3,8 +3,11 @@ quantisation by this package's HIP kernels, GEMM + dequantisation through `torch
 (hipBLASLt fp8 MFMA on gfx950, OCP e4m3fn) -- the reference's own route on ROCm, where its CUTLASS
 kernels do not exist.  AWQ W4A16 (backends/quantization/awq.py): load-time repack and the gfx950
 weight-streaming kernel with in-register dequantisation.  W8A8 int8 (w8a8_utils.py:192-209): per-token activation
-quantisation and the int32-accumulating weight-streaming kernel, where the reference calls CUTLASS."""
+quantisation and the int32-accumulating weight-streaming kernel, where the reference calls CUTLASS.  W4A8 MXFP4 (OCP microscaling; not in the
+reference): fp4 weights with E8M0 block scales streamed into gfx950's scaled MFMA against fp8 activations."""
 from .awq import AWQConfig, apply_awq_linear, pack_awq_weight, quantize_awq  # noqa: F401
 from .fp8 import (apply_fp8_linear, pack_fp8_weight, per_tensor_quantize_weight,  # noqa: F401
                   skinny_fp8_linear)
 from .int8 import apply_int8_linear, pack_int8_weight, quantize_int8_weight  # noqa: F401
+from .mxfp4 import (apply_mxfp4_linear, dequantize_mxfp4, pack_mxfp4_weight,  # noqa: F401
+                    quantize_mxfp4_weight)

@@ -401,6 +401,82 @@ if len(sys.argv) > 1 and sys.argv[1] == "--int8-prefill":
     int8_prefill_leg(sys.argv[2] if len(sys.argv) > 2 else None)
     sys.exit(0)
 
+def mxfp4_leg(out_path):
+    """--mxfp4 [out.md]: the W4A8 MXFP4 launch (fp8 activations quantised beforehand, per-token scales) against the
+    fp8 W8A8 decode launch (skinny_linear_w8a8_q on pre-quantised activations up to 32 rows; at 64 rows
+    skinny_linear_w8a8, which quantises 16-bit activations in its prologue) and the AWQ W4A16 decode launch (G = 128),
+    same process.  The method is the other legs': weights rotate through > 1 GB of buffers per format, 5 warm-up
+    launches, REGIONS regions of PER launches, the formats alternating launch by launch; a region's figure is the
+    median of its device-event times, every region is listed."""
+    REGIONS, PER, G = 5, 40, 128
+    shapes = [("qkv", 6144, 4096), ("o", 4096, 4096), ("gate_up", 28672, 4096), ("down", 4096, 14336)]
+    fmt = lambda r: " ".join(f"{t:.1f}" for t in r)  # noqa: E731
+    med = lambda r: sorted(r)[len(r) // 2]  # noqa: E731
+    lines = ["| shape | M | mxfp4 us (regions) | fp8 us (regions) | AWQ us (regions) | mxfp4 TB/s | fp8 TB/s | "
+             "AWQ TB/s | mxfp4 vs fp8 | mxfp4 vs AWQ |", "|---|---|---|---|---|---|---|---|---|---|"]
+    one = torch.ones(1, device=dev)
+
+    def verdict(a, b):
+        word = "SLOWER beyond" if min(a) > max(b) else "faster beyond" if max(a) < min(b) else "within"
+        return f"{med(a) / med(b):.2f}x the time, {word} the spread"
+
+    for name, N, K in shapes:
+        wp, ep = torch.ops._C_amd.mxfp4_pack(torch.randint(0, 256, (N, K // 2), device=dev, dtype=torch.uint8),
+                                             torch.randint(117, 130, (N, K // 32), device=dev, dtype=torch.uint8))
+        w8 = torch.ops._C_amd.int8_pack(torch.randint(-120, 120, (N, K), device=dev, dtype=torch.int8)).view(torch.uint8)
+        qw = torch.randint(-2 ** 31, 2 ** 31, (K, N // 8), device=dev, dtype=torch.int64).to(torch.int32)
+        qz = torch.randint(-2 ** 31, 2 ** 31, (K // G, N // 8), device=dev, dtype=torch.int64).to(torch.int32)
+        w4, meta = torch.ops._C_amd.awq_pack(qw, qz, (torch.rand(K // G, N, device=dev) * 0.01 + 1e-3).to(torch.bfloat16))
+        del qw, qz
+        bmx, b8, b4 = wp.numel() + ep.numel(), N * K, w4.numel() * 4 + meta.numel() * 4
+        nmx, n8, n4 = (min(160, int(1.1e9 // b) + 1) for b in (bmx, b8, b4))
+        mxs, w8s = [(wp.clone(), ep.clone()) for _ in range(nmx)], [w8.clone() for _ in range(n8)]
+        w4s = [(w4.clone(), meta.clone()) for _ in range(n4)]
+        for M in (1, 8, 32, 64):
+            x8 = torch.randint(0, 120, (M, K), device=dev, dtype=torch.uint8).view(torch.float8_e4m3fn)  # finite values
+            x16 = (torch.randn(M, K, device=dev) * 0.5).to(torch.bfloat16)
+            sx = torch.rand(M, device=dev) * 1e-2 + 1e-3
+            fs = [lambda i: torch.ops._C_amd.skinny_linear_w4a8_mxfp4(x8, mxs[i % nmx][0], mxs[i % nmx][1], sx, N, K, None,
+                                                                      torch.bfloat16),
+                  (lambda i: torch.ops._C_amd.skinny_linear_w8a8_q(x8, w8s[i % n8], one, one, N, K, None, torch.bfloat16))
+                  if M <= 32 else (lambda i: torch.ops._C_amd.skinny_linear_w8a8(x16, w8s[i % n8], one, one, N, K, None)),
+                  lambda i: torch.ops._C_amd.skinny_linear_w4a16(x16, w4s[i % n4][0], w4s[i % n4][1], N, K, G, None)]
+            for i in range(5):
+                for f in fs:
+                    f(i)
+            torch.cuda.synchronize()
+            regions, it = [[] for _ in fs], 0
+            for _ in range(REGIONS):
+                evs = []
+                for _ in range(PER):
+                    e = [torch.cuda.Event(enable_timing=True) for _ in range(len(fs) + 1)]
+                    e[0].record()
+                    for j, f in enumerate(fs):
+                        f(it)
+                        e[j + 1].record()
+                    evs.append(e)
+                    it += 1
+                torch.cuda.synchronize()
+                for j in range(len(fs)):
+                    regions[j].append(med([e[j].elapsed_time(e[j + 1]) * 1e3 for e in evs]))
+            rmx, r8, r4 = regions
+            tot = [bmx + M * K + M * N * 2 + 4 * M, b8 + M * K * (1 if M <= 32 else 2) + M * N * 2,
+                   b4 + M * K * 2 + M * N * 2]
+            lines.append(f"| {name} {N}x{K} | {M} | {med(rmx):.1f} ({fmt(rmx)}) | {med(r8):.1f} ({fmt(r8)}) | "
+                         f"{med(r4):.1f} ({fmt(r4)}) | {tot[0] / med(rmx) / 1e6:.2f} | {tot[1] / med(r8) / 1e6:.2f} | "
+                         f"{tot[2] / med(r4) / 1e6:.2f} | {verdict(rmx, r8)} | {verdict(rmx, r4)} |")
+            print(lines[-1], flush=True)
+        del mxs, w8s, w4s
+        torch.cuda.empty_cache()
+    if out_path:
+        with open(out_path, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if len(sys.argv) > 1 and sys.argv[1] == "--mxfp4":
+    mxfp4_leg(sys.argv[2] if len(sys.argv) > 2 else None)
+    sys.exit(0)
+
 if len(sys.argv) > 1 and sys.argv[1] == "--int8":
     int8_leg(sys.argv[2] if len(sys.argv) > 2 else None)
     sys.exit(0)
