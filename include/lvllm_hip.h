@@ -71,7 +71,8 @@ const char* lvllm_version(void);
  * kernel instead of dequantising the packed weight for the library GEMM; min_rows huge = never), "fp8_tiled_min_rows"
  * and "fp8_tiled_max_rows" (the Python layer's W8A8 fp8 linear, apply_fp8_linear with a packed weight: the range of
  * row counts that quantise without padding and take the LDS-tiled kernel instead of torch._scaled_mm; min above max =
- * never).  lvllm_get_tuning reads a knob back. */
+ * never), "mxfp4_tiled_min_rows" (the torch layer's W4A8 MXFP4 linear: row count from which the LDS-tiled kernel runs
+ * instead of 64-row chunks of the streaming one; a huge value = never).  lvllm_get_tuning reads a knob back. */
 int lvllm_set_tuning(const char* key, int value);
 int lvllm_get_tuning(const char* key, int* value);
 
@@ -667,6 +668,23 @@ int64_t lvllm_skinny_gemm_w4a8_mxfp4_workspace_bytes(int M, int N, int K);
 int lvllm_skinny_gemm_w4a8_mxfp4(void* y, const void* x_fp8, const void* w_packed, const void* e_packed,
                                  const float* x_scale, const void* bias, int M, int N, int K, int64_t ldx, int dtype,
                                  void* workspace, int64_t workspace_bytes, void* stream);
+
+/* lvllm_gemm_w4a8_mxfp4 (csrc/mxfp4_tiled_gemm.hip): the same product for ANY M >= 1 -- the LDS-tiled,
+ * operand-reusing kernel for prefill batches (meant for M > 64) on v_mfma_scale_f32_16x16x128_f8f6f4, fp4 x fp8.
+ * y [M, N] = T(x_scale[m] * acc + bias[n]), acc the fp32 sum of the scaled MFMA, the scale and the bias applied in
+ * fp32 in that order, one rounding to T = bf16 / f16.  x_fp8 [M, K] e4m3fn bytes ALREADY quantised, rows ldx BYTES
+ * apart; w_packed / e_packed the pair of lvllm_mxfp4_pack, read as it is; x_scale fp32 [M]; bias [N] of T or null.
+ * N % 16 == 0, K % 128 == 0, K < 131072, N * K / 2 < 2^32 - 16, ldx >= K, ldx % 16 == 0, (M - 1) * ldx + K < 2^31,
+ * x_fp8 / w_packed 16-byte aligned, e_packed 4-byte, y 8-byte aligned; returns 3 and launches nothing outside the
+ * envelope.  workspace: fp32 split-K partials for launches with fewer output tiles than the device holds workgroups
+ * (K is split in whole scale words of 512 k, at least 1024 k per split), lvllm_gemm_w4a8_mxfp4_workspace_bytes(M, N,
+ * K) bytes (0 when K is not split), 16-byte aligned; ask again after lvllm_set_tuning("gemm_workgroups", ...), which
+ * the split follows.  The partials are summed in the order of the splits: the result is deterministic for a shape and
+ * tuning, but may differ in the last bit between two splits. */
+int64_t lvllm_gemm_w4a8_mxfp4_workspace_bytes(int M, int N, int K);
+int lvllm_gemm_w4a8_mxfp4(void* y, const void* x_fp8, const void* w_packed, const void* e_packed, const float* x_scale,
+                          const void* bias, int M, int N, int K, int64_t ldx, int dtype, void* workspace,
+                          int64_t workspace_bytes, void* stream);
 
 /* ---- device queries (csrc/cuda_utils.h, torch_bindings.cpp:271-279) ------- */
 int64_t lvllm_get_device_attribute(int64_t attribute, int64_t device_id);

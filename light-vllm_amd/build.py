@@ -37,6 +37,7 @@ HIP_SOURCES = [
     "int8_tiled_gemm.hip",
     "fp8_tiled_gemm.hip",
     "mxfp4_gemm.hip",
+    "mxfp4_tiled_gemm.hip",
     "prefill_attention.hip",
     "prepare_inputs.hip",
     "fp8_quant.hip",

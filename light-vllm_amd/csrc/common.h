@@ -31,6 +31,7 @@ void set_error(const std::string& msg);
 //   int8_tiled_min_rows    see Tuning
 //   w4_tiled_min_rows, w4_tiled_max_rows    see Tuning
 //   fp8_tiled_min_rows, fp8_tiled_max_rows  see Tuning
+//   mxfp4_tiled_min_rows   see Tuning
 struct Tuning {
   int gemm_workgroups = 256;
   int gemm_workgroups_wide = 0;  // for projections with >= gemm_wide_min_tiles n-tiles; 0 = as above
@@ -73,6 +74,11 @@ struct Tuning {
                                 // gate_up at every measured M and on all four 8B projections from 512 rows on; with
                                 // per-token x per-channel scales the tiled route wins on all four at 65 .. 2048 rows,
                                 // set (65, 2048) there (profiles/fp8_tiled_gemm.md)
+  int mxfp4_tiled_min_rows = 256;  // W4A8 MXFP4 linear: launches with at least this many rows take the LDS-tiled kernel
+                                   // (mxfp4_tiled_gemm.hip), fewer run the weight-streaming kernel in chunks of 64
+                                   // rows.  Measured (profiles/mxfp4_tiled_gemm.md): faster beyond the spread on all
+                                   // four 8B projections from 256 rows on, slower on qkv and o at 65 and 128 rows and on
+                                   // gate_up at 128; a huge value = always the chunks
 };
 Tuning& tuning();
 

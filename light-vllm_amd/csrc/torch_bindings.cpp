@@ -1510,12 +1510,13 @@ std::tuple<torch::Tensor, torch::Tensor> mxfp4_pack(const torch::Tensor& codes, 
   return {w, e};
 }
 
-// y [M, N] = T(sx[m] * (x_fp8 . W^T)[m, n] + bias[n]) from the packed pair, any M >= 1: above 64 rows the same kernel
-// runs over chunks of 64 rows (row for row the <= 64 result; the weights stream once per chunk).
-torch::Tensor skinny_linear_w4a8_mxfp4(const torch::Tensor& x_in, const torch::Tensor& w_packed,
-                                       const torch::Tensor& e_packed, const torch::Tensor& x_scale, int64_t N, int64_t K,
-                                       const std::optional<torch::Tensor>& bias, at::ScalarType out_dtype) {
-  const char* op = "skinny_linear_w4a8_mxfp4";
+// y [M, N] = T(sx[m] * (x_fp8 . W^T)[m, n] + bias[n]) from the packed pair, any M >= 1.  From tuning
+// "mxfp4_tiled_min_rows" rows on (or always, with `tiled`) the LDS-tiled kernel reads the weights once per launch;
+// below, the streaming kernel runs over chunks of 64 rows (row for row the <= 64 result; the weights stream once per
+// chunk).
+torch::Tensor mxfp4_linear(const torch::Tensor& x_in, const torch::Tensor& w_packed, const torch::Tensor& e_packed,
+                           const torch::Tensor& x_scale, int64_t N, int64_t K, const std::optional<torch::Tensor>& bias,
+                           at::ScalarType out_dtype, const char* op, bool tiled) {
   LV_CHECK_DEVICE(x_in);
   LV_CHECK_DEVICE(w_packed);
   LV_CHECK_DEVICE(e_packed);
@@ -1538,10 +1539,25 @@ torch::Tensor skinny_linear_w4a8_mxfp4(const torch::Tensor& x_in, const torch::T
                           ((uintptr_t)x_in.data_ptr() & 15) == 0;
   const torch::Tensor x = strided_ok ? x_in : x_in.contiguous();
   const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(device_of(x));
-  const int64_t ws_bytes = lvllm_skinny_gemm_w4a8_mxfp4_workspace_bytes((int)std::min<int64_t>(M, 64), (int)N, (int)K);
+  TORCH_CHECK(M < ((int64_t)1 << 31), op, ": too many rows");
+  // one descriptor spans all rows of the tiled launch: an X that reaches past 2 GiB stays with the 64-row chunks,
+  // each of which has a descriptor of its own
+  const bool one_descriptor = (M - 1) * x.stride(0) + K < ((int64_t)1 << 31);
+  TORCH_CHECK(!tiled || one_descriptor, op, ": x_fp8 spans 2 GiB or more");
+  int min_rows = 0;
+  check(lvllm_get_tuning("mxfp4_tiled_min_rows", &min_rows));
+  tiled = tiled || (M >= min_rows && one_descriptor);
+  const int64_t ws_bytes = tiled ? lvllm_gemm_w4a8_mxfp4_workspace_bytes((int)M, (int)N, (int)K)
+                                 : lvllm_skinny_gemm_w4a8_mxfp4_workspace_bytes((int)std::min<int64_t>(M, 64), (int)N, (int)K);
   torch::Tensor ws;
   if (ws_bytes > 0) ws = torch::empty({ws_bytes / 4}, x.options().dtype(torch::kFloat));
   const int dt = out_dtype == at::kBFloat16 ? LVLLM_BF16 : LVLLM_F16;
+  if (tiled) {
+    check(lvllm_gemm_w4a8_mxfp4(y.data_ptr(), x.data_ptr(), w_packed.data_ptr(), e_packed.data_ptr(), sx.data_ptr<float>(),
+                                bias ? bias->data_ptr() : nullptr, (int)M, (int)N, (int)K, x.stride(0), dt,
+                                ws_bytes > 0 ? ws.data_ptr() : nullptr, ws_bytes, current_stream(x)));
+    return y;
+  }
   for (int64_t m0 = 0; m0 < M; m0 += 64) {
     const int64_t rows = std::min<int64_t>(64, M - m0);
     check(lvllm_skinny_gemm_w4a8_mxfp4((char*)y.data_ptr() + m0 * N * 2, (const char*)x.data_ptr() + m0 * x.stride(0),
@@ -1550,6 +1566,19 @@ torch::Tensor skinny_linear_w4a8_mxfp4(const torch::Tensor& x_in, const torch::T
                                        ws_bytes > 0 ? ws.data_ptr() : nullptr, ws_bytes, current_stream(x)));
   }
   return y;
+}
+
+torch::Tensor skinny_linear_w4a8_mxfp4(const torch::Tensor& x_fp8, const torch::Tensor& w_packed,
+                                       const torch::Tensor& e_packed, const torch::Tensor& x_scale, int64_t N, int64_t K,
+                                       const std::optional<torch::Tensor>& bias, at::ScalarType out_dtype) {
+  return mxfp4_linear(x_fp8, w_packed, e_packed, x_scale, N, K, bias, out_dtype, "skinny_linear_w4a8_mxfp4", false);
+}
+
+// the tiled kernel at any M: what tests and benchmarks address directly
+torch::Tensor linear_w4a8_mxfp4_tiled(const torch::Tensor& x_fp8, const torch::Tensor& w_packed,
+                                      const torch::Tensor& e_packed, const torch::Tensor& x_scale, int64_t N, int64_t K,
+                                      const std::optional<torch::Tensor>& bias, at::ScalarType out_dtype) {
+  return mxfp4_linear(x_fp8, w_packed, e_packed, x_scale, N, K, bias, out_dtype, "linear_w4a8_mxfp4_tiled", true);
 }
 
 int64_t get_device_attribute(int64_t attribute, int64_t device_id) {
@@ -1702,6 +1731,10 @@ TORCH_LIBRARY(_C_amd, amd) {
   amd.def("skinny_linear_w4a8_mxfp4(Tensor x_fp8, Tensor w_packed, Tensor e_packed, Tensor x_scale, int N, int K, "
           "Tensor? bias, ScalarType out_dtype) -> Tensor");
   amd.impl("skinny_linear_w4a8_mxfp4", torch::kCUDA, &skinny_linear_w4a8_mxfp4);
+  // W4A8 MXFP4 for prefill batches: always the LDS-tiled kernel, the same packed pair
+  amd.def("linear_w4a8_mxfp4_tiled(Tensor x_fp8, Tensor w_packed, Tensor e_packed, Tensor x_scale, int N, int K, "
+          "Tensor? bias, ScalarType out_dtype) -> Tensor");
+  amd.impl("linear_w4a8_mxfp4_tiled", torch::kCUDA, &linear_w4a8_mxfp4_tiled);
   // W8A8 fp8 for prefill batches: activations already fp8 (scaled_fp8_quant), the decode kernel's packed weight
   amd.def("linear_w8a8_fp8_tiled(Tensor x_fp8, Tensor w_packed, Tensor x_scale, Tensor w_scale, int N, int K, "
           "Tensor? bias, ScalarType out_dtype) -> Tensor");

@@ -473,6 +473,89 @@ def mxfp4_leg(out_path):
             f.write("\n".join(lines) + "\n")
 
 
+def mxfp4_prefill_leg(out_path):
+    """--mxfp4-prefill [out.md]: (a) the LDS-tiled W4A8 MXFP4 GEMM (linear_w4a8_mxfp4_tiled) against (b) the 64-row
+    chunks of the streaming kernel (skinny_linear_w4a8_mxfp4 with mxfp4_tiled_min_rows huge: what the linear did before
+    the tiled kernel) and, for context only, (c) the LDS-tiled W8A8 fp8 GEMM on the same shapes.  bf16 output,
+    activations quantised beforehand, per-token scales.  The method of --mxfp4: same process, weights rotate through
+    > 1 GB of buffers per format, 5 warm-up launches, then REGIONS regions of PER launches, the legs alternating launch
+    by launch; a region's figure is the median of its device-event times and every region is listed.  The tuning key
+    is set once, outside the timed spans.  Before timing, each row asserts (a) within two bf16 ulps at the output's
+    scale of (b).  The last lines name the smallest M from which (a) is faster beyond the spread on all four shapes
+    and stays so."""
+    REGIONS, PER = 5, 40
+    MS = (65, 128, 256, 512, 1024, 2048, 8192)
+    shapes = [("qkv", 6144, 4096), ("o", 4096, 4096), ("gate_up", 28672, 4096), ("down", 4096, 14336)]
+    fmt = lambda r: " ".join(f"{t:.0f}" for t in r)  # noqa: E731
+    med = lambda r: sorted(r)[len(r) // 2]  # noqa: E731
+    get, put = torch.ops._C_amd.get_tuning, torch.ops._C_amd.set_tuning
+    default_rows = get("mxfp4_tiled_min_rows")
+    lines = ["| shape | M | tiled us (regions) | chunks of 64 us (regions) | fp8 tiled us (regions) | tiled Tflop/s | "
+             "chunks Tflop/s | fp8 tiled Tflop/s | tiled vs chunks |", "|---|---|---|---|---|---|---|---|---|"]
+    put("mxfp4_tiled_min_rows", 1 << 30)  # skinny_linear_w4a8_mxfp4 = the chunks from here on
+    wins = {M: 0 for M in MS}
+    one = torch.ones(1, device=dev)
+    for name, N, K in shapes:
+        wp, ep = torch.ops._C_amd.mxfp4_pack(torch.randint(0, 256, (N, K // 2), device=dev, dtype=torch.uint8),
+                                             torch.randint(117, 130, (N, K // 32), device=dev, dtype=torch.uint8))
+        w8 = torch.randint(0, 120, (N * K,), device=dev, dtype=torch.uint8)  # packing permutes bytes: any finite ones do
+        nmx, n8 = min(160, int(1.1e9 // (wp.numel() + ep.numel())) + 1), int(1.1e9 // (N * K)) + 1
+        mxs, w8s = [(wp.clone(), ep.clone()) for _ in range(nmx)], [w8.clone() for _ in range(n8)]
+        for M in MS:
+            x8 = torch.randint(0, 120, (M, K), device=dev, dtype=torch.uint8).view(torch.float8_e4m3fn)  # finite values
+            sx = torch.rand(M, device=dev) * 1e-2 + 1e-3
+            fs = [lambda i: torch.ops._C_amd.linear_w4a8_mxfp4_tiled(x8, mxs[i % nmx][0], mxs[i % nmx][1], sx, N, K, None,
+                                                                     torch.bfloat16),
+                  lambda i: torch.ops._C_amd.skinny_linear_w4a8_mxfp4(x8, mxs[i % nmx][0], mxs[i % nmx][1], sx, N, K, None,
+                                                                      torch.bfloat16),
+                  lambda i: torch.ops._C_amd.linear_w8a8_fp8_tiled(x8, w8s[i % n8], sx, one, N, K, None, torch.bfloat16)]
+            ya, yb = fs[0](0).float(), fs[1](0).float()
+            assert (ya - yb).abs().max().item() <= 2 ** -7 * yb.abs().max().item(), (name, M)
+            del ya, yb
+            for i in range(5):
+                for f in fs:
+                    f(i)
+            torch.cuda.synchronize()
+            regions, it = [[] for _ in fs], 0
+            for _ in range(REGIONS):
+                evs = []
+                for _ in range(PER):
+                    e = [torch.cuda.Event(enable_timing=True) for _ in range(len(fs) + 1)]
+                    e[0].record()
+                    for j, f in enumerate(fs):
+                        f(it)
+                        e[j + 1].record()
+                    evs.append(e)
+                    it += 1
+                torch.cuda.synchronize()
+                for j in range(len(fs)):
+                    regions[j].append(med([e[j].elapsed_time(e[j + 1]) * 1e3 for e in evs]))
+            rt, rc, r8 = regions
+            flop = 2.0 * M * N * K
+            wins[M] += max(rt) < min(rc)
+            verdict = ("faster beyond the spread" if max(rt) < min(rc) else
+                       "SLOWER beyond the spread" if min(rt) > max(rc) else "within the spread")
+            lines.append(f"| {name} {N}x{K} | {M} | {med(rt):.1f} ({fmt(rt)}) | {med(rc):.1f} ({fmt(rc)}) | "
+                         f"{med(r8):.1f} ({fmt(r8)}) | {flop / med(rt) / 1e6:.0f} | {flop / med(rc) / 1e6:.0f} | "
+                         f"{flop / med(r8) / 1e6:.0f} | {med(rc) / med(rt):.2f}x, {verdict} |")
+            print(lines[-1], flush=True)
+        del mxs, w8s
+        torch.cuda.empty_cache()
+    put("mxfp4_tiled_min_rows", default_rows)
+    ahead = [M for i, M in enumerate(MS) if all(wins[m] == len(shapes) for m in MS[i:])]
+    lines += ["", f"tiled faster beyond the spread on all {len(shapes)} shapes from M = {ahead[0]} on" if ahead else
+              "no M from which the tiled kernel is faster beyond the spread on all shapes and stays so",
+              f"mxfp4_tiled_min_rows of this build: {default_rows}"]
+    print("\n".join(lines[-2:]), flush=True)
+    if out_path:
+        with open(out_path, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if len(sys.argv) > 1 and sys.argv[1] == "--mxfp4-prefill":
+    mxfp4_prefill_leg(sys.argv[2] if len(sys.argv) > 2 else None)
+    sys.exit(0)
+
 if len(sys.argv) > 1 and sys.argv[1] == "--mxfp4":
     mxfp4_leg(sys.argv[2] if len(sys.argv) > 2 else None)
     sys.exit(0)
