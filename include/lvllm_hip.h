@@ -72,7 +72,10 @@ const char* lvllm_version(void);
  * and "fp8_tiled_max_rows" (the Python layer's W8A8 fp8 linear, apply_fp8_linear with a packed weight: the range of
  * row counts that quantise without padding and take the LDS-tiled kernel instead of torch._scaled_mm; min above max =
  * never), "mxfp4_tiled_min_rows" (the torch layer's W4A8 MXFP4 linear: row count from which the LDS-tiled kernel runs
- * instead of 64-row chunks of the streaming one; a huge value = never).  lvllm_get_tuning reads a knob back. */
+ * instead of 64-row chunks of the streaming one; a huge value = never), "dense_tiled_min_rows" and
+ * "dense_tiled_max_rows" (the Python layer's 16-bit linear above 64 rows: the range of row counts that take the
+ * LDS-tiled kernel with its fused epilogue, lvllm_tiled_gemm, instead of the library GEMM and a separate activation
+ * launch; min above max = never, the default 65 / 0).  lvllm_get_tuning reads a knob back. */
 int lvllm_set_tuning(const char* key, int value);
 int lvllm_get_tuning(const char* key, int* value);
 
@@ -273,6 +276,25 @@ int64_t lvllm_stream_gemm_workspace_bytes(int M, int N, int K);
 int lvllm_stream_gemm(void* y, const void* x, const void* w_packed, const void* bias, int M, int N,
                       int K, int64_t ldx, int dtype, void* workspace, int64_t workspace_bytes,
                       void* stream);
+/* lvllm_tiled_gemm (csrc/dense_tiled_gemm.hip): the same product for ANY M >= 1 -- the LDS-tiled, operand-reusing
+ * kernel for prefill batches (meant for M > 64) on v_mfma_f32_16x16x32_bf16 / _f16, fp32 accumulation, with the
+ * activation in its epilogue.  x [M, K] of T = bf16 / f16, rows ldx ELEMENTS apart; w_packed by lvllm_pack_weight,
+ * read as the decode kernels read it; bias [N] of T or null; y rows ldy ELEMENTS apart.
+ *   act = 0: y [M, N] = T(acc + float(bias[n])), one rounding;
+ *   act = 1: y [M, N] = GELU of that rounded value, bit for bit what lvllm_gelu leaves on the act = 0 result;
+ *   act = 2: W rows are [gate (N/2) | up (N/2)] and y is [M, N/2], bit for bit what lvllm_silu_and_mul leaves on the
+ *            act = 0 result (K is never split).
+ * N % 16 == 0 (N % 32 == 0 for act = 2), K % 32 == 0, packed weight below 4 GiB, ldx >= K, ldx % 8 == 0, ldy >= the
+ * output width, ldy % 4 == 0, ((M - 1) * ldx + K) * 2 < 2^31, x / w_packed 16-byte aligned, y 8-byte aligned; returns 3
+ * and launches nothing outside the envelope, lvllm_last_error names the argument.
+ * workspace: fp32 split-K partials for launches with fewer output tiles than the device holds workgroups,
+ * lvllm_tiled_gemm_workspace_bytes(M, N, K) bytes (0 when K is not split), 16-byte aligned; ask again after
+ * lvllm_set_tuning("gemm_workgroups", ...), which the split follows.  The partials are summed in the order of the
+ * splits: the result is deterministic for a shape and tuning, but may differ in the last bit between two splits. */
+int64_t lvllm_tiled_gemm_workspace_bytes(int M, int N, int K);
+int lvllm_tiled_gemm(void* y, const void* x, const void* w_packed, const void* bias, int M, int N, int K,
+                     int64_t ldx, int64_t ldy, int dtype, int act, void* workspace, int64_t workspace_bytes,
+                     void* stream);
 /* As lvllm_skinny_gemm, plus: act = 1 -> X rows are [gate | up] (2K wide) and the kernel
  * multiplies by T(T(silu(gate)) * up) (silu_and_mul fused into the down projection);
  * act = 2 -> W rows are [gate (N/2) | up (N/2)] and y is [M, N/2] = silu_and_mul of the projection,

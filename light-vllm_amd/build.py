@@ -31,6 +31,7 @@ HIP_SOURCES = [
     "attention_bf16.hip",
     "attention_f16.hip",
     "skinny_gemm.hip",
+    "dense_tiled_gemm.hip",
     "awq_gemm.hip",
     "awq_tiled_gemm.hip",
     "int8_gemm.hip",

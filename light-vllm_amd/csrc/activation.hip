@@ -6,16 +6,9 @@
 //   before the T x T multiply).
 // Launch: flat grid over 16-byte chunks (not one block per token): at decode
 // batch sizes a per-token grid leaves most of the 256 CUs idle.
-#include "common.h"
+#include "activation.h"
 
 namespace lvllm {
-
-template <typename T>
-__device__ inline typename T::store_t silu_mul(typename T::store_t x, typename T::store_t y) {
-  const float xf = T::to_float(x);
-  const typename T::store_t a = T::from_float(xf / (1.0f + expf(-xf)));
-  return T::from_float(T::to_float(a) * T::to_float(y));
-}
 
 template <typename T>
 __global__ void silu_and_mul_vec_kernel(typename T::store_t* __restrict__ out,
@@ -95,10 +88,7 @@ __global__ void gelu_vec_kernel(typename T::store_t* out, const typename T::stor
     const V a = reinterpret_cast<const V*>(x)[idx];
     V o;
 #pragma unroll
-    for (int j = 0; j < N; ++j) {
-      const float f = T::to_float(a.v[j]);
-      o.v[j] = T::from_float(f * 0.5f * (1.0f + erff(f * 0.70710678118654752440f)));
-    }
+    for (int j = 0; j < N; ++j) o.v[j] = gelu_erf<T>(a.v[j]);
     reinterpret_cast<V*>(out)[idx] = o;
   }
 }

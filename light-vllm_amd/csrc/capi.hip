@@ -89,6 +89,12 @@ extern "C" int lvllm_set_tuning(const char* key, int value) {
   } else if (k == "mxfp4_tiled_min_rows") {
     LV_CHECK(value >= 1, "mxfp4_tiled_min_rows must be positive (a huge value: never)");
     lvllm::tuning().mxfp4_tiled_min_rows = value;
+  } else if (k == "dense_tiled_min_rows") {
+    LV_CHECK(value >= 1, "dense_tiled_min_rows must be positive (above dense_tiled_max_rows: never)");
+    lvllm::tuning().dense_tiled_min_rows = value;
+  } else if (k == "dense_tiled_max_rows") {
+    LV_CHECK(value >= 0, "dense_tiled_max_rows must be non-negative (0: never)");
+    lvllm::tuning().dense_tiled_max_rows = value;
   } else {
     LV_CHECK(false, "unknown tuning key '" + k + "'");
   }
@@ -120,6 +126,8 @@ extern "C" int lvllm_get_tuning(const char* key, int* value) {
   else if (k == "fp8_tiled_min_rows") *value = t.fp8_tiled_min_rows;
   else if (k == "fp8_tiled_max_rows") *value = t.fp8_tiled_max_rows;
   else if (k == "mxfp4_tiled_min_rows") *value = t.mxfp4_tiled_min_rows;
+  else if (k == "dense_tiled_min_rows") *value = t.dense_tiled_min_rows;
+  else if (k == "dense_tiled_max_rows") *value = t.dense_tiled_max_rows;
   else LV_CHECK(false, "unknown tuning key '" + k + "'");
   return 0;
 }

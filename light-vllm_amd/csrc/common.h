@@ -32,6 +32,7 @@ void set_error(const std::string& msg);
 //   w4_tiled_min_rows, w4_tiled_max_rows    see Tuning
 //   fp8_tiled_min_rows, fp8_tiled_max_rows  see Tuning
 //   mxfp4_tiled_min_rows   see Tuning
+//   dense_tiled_min_rows, dense_tiled_max_rows  see Tuning
 struct Tuning {
   int gemm_workgroups = 256;
   int gemm_workgroups_wide = 0;  // for projections with >= gemm_wide_min_tiles n-tiles; 0 = as above
@@ -79,6 +80,11 @@ struct Tuning {
                                    // rows.  Measured (profiles/mxfp4_tiled_gemm.md): faster beyond the spread on all
                                    // four 8B projections from 256 rows on, slower on qkv and o at 65 and 128 rows and on
                                    // gate_up at 128; a huge value = always the chunks
+  int dense_tiled_min_rows = 65;  // 16-bit linear above the streaming kernels' rows (engine/model.py, prefill_only/
+  int dense_tiled_max_rows = 0;   // model.py with tiled_mlp): calls with min_rows <= M <= max_rows take the LDS-tiled
+                                  // kernel with its bias / GELU / SwiGLU epilogue (dense_tiled_gemm.hip), the others
+                                  // the library GEMM and a separate activation launch.  min above max = never, the
+                                  // default (profiles/dense_tiled_gemm.md)
 };
 Tuning& tuning();
 

@@ -376,6 +376,37 @@ torch::Tensor stream_linear_packed(const torch::Tensor& x, const torch::Tensor& 
   return y;
 }
 
+// Any row count (meant for prefill batches): the LDS-tiled kernel with its epilogue, see lvllm_tiled_gemm.  act 0:
+// x . w^T + bias; 1: GELU of it; 2: w_packed holds [gate rows | up rows] and the result is [M, N / 2] = silu_and_mul
+// of it.  Bit-identical to act 0 followed by gelu / silu_and_mul.  Outside the kernel's envelope it raises.
+torch::Tensor linear_tiled(const torch::Tensor& x, const torch::Tensor& w_packed,
+                           const std::optional<torch::Tensor>& bias, int64_t N, int64_t K, int64_t act) {
+  TORCH_CHECK(x.dim() == 2 && x.size(1) == K && w_packed.numel() == N * K && x.stride(1) == 1 && N > 0 &&
+                  N < ((int64_t)1 << 31) && x.size(0) < ((int64_t)1 << 31),
+              "linear_tiled: x [M, K] with unit column stride, w_packed of N * K elements");
+  TORCH_CHECK(x.is_cuda() && w_packed.is_cuda() && w_packed.is_contiguous() &&
+                  (x.scalar_type() == at::kBFloat16 || x.scalar_type() == at::kHalf) &&
+                  w_packed.scalar_type() == x.scalar_type() &&
+                  (!bias || (bias->is_cuda() && bias->is_contiguous() && bias->numel() == N &&
+                             bias->scalar_type() == x.scalar_type())),
+              "linear_tiled: bf16/f16 x, w_packed and bias [N] of one type on the GPU");
+  TORCH_CHECK(act >= 0 && act <= 2, "linear_tiled: act must be 0 (bias), 1 (GELU) or 2 (SwiGLU)");
+  const int64_t M = x.size(0);
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(device_of(x));
+  const int64_t width = act == 2 ? N / 2 : N;
+  auto y = torch::empty({M, width}, x.options());
+  if (M == 0) return y;
+  const int64_t ws_bytes = act == 2 ? 0 : lvllm_tiled_gemm_workspace_bytes((int)M, (int)N, (int)K);
+  torch::Tensor ws;
+  if (ws_bytes > 0) ws = torch::empty({ws_bytes / 4}, x.options().dtype(torch::kFloat));
+  const int rc = lvllm_tiled_gemm(y.data_ptr(), x.data_ptr(), w_packed.data_ptr(), bias ? bias->data_ptr() : nullptr,
+                                  (int)M, (int)N, (int)K, x.stride(0), width, dtype_code(x, "linear_tiled"), (int)act,
+                                  ws_bytes > 0 ? ws.data_ptr() : nullptr, ws_bytes, current_stream(x));
+  TORCH_CHECK(rc != 3, lvllm_last_error());
+  check(rc);
+  return y;
+}
+
 // gate_up projection + silu_and_mul in one launch: w_packed holds [gate rows | up rows] ([N, K]
 // packed), the result is [M, N / 2].  Bit-identical to skinny_linear_packed followed by silu_and_mul.
 torch::Tensor skinny_linear_packed_swiglu(const torch::Tensor& x, const torch::Tensor& w_packed,
@@ -1747,6 +1778,8 @@ TORCH_LIBRARY(_C_amd, amd) {
   amd.impl("skinny_linear_packed_argmax", torch::kCUDA, &skinny_linear_packed_argmax);
   amd.def("stream_linear_packed(Tensor x, Tensor w_packed, Tensor? bias, int N, int K) -> Tensor");
   amd.impl("stream_linear_packed", torch::kCUDA, &stream_linear_packed);
+  amd.def("linear_tiled(Tensor x, Tensor w_packed, Tensor? bias, int N, int K, int act) -> Tensor");
+  amd.impl("linear_tiled", torch::kCUDA, &linear_tiled);
   amd.def("skinny_linear_packed_swiglu(Tensor x, Tensor w_packed, Tensor? bias, int N, int K) -> Tensor");
   amd.impl("skinny_linear_packed_swiglu", torch::kCUDA, &skinny_linear_packed_swiglu);
   amd.def("skinny_linear_packed_partials(Tensor x, Tensor w_packed, int N, int K, bool swiglu) -> Tensor");

@@ -115,7 +115,8 @@ class Weight:
 
 def linear(x: torch.Tensor, w: "Weight", bias: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Dense projection.  Decode batches (<= 64 rows) stream the weights through the gfx950
-    weight-streaming kernel; larger batches use the library GEMM (hipBLASLt)."""
+    weight-streaming kernel; larger batches use the library GEMM (hipBLASLt) or, where tuning dense_tiled_min_rows ..
+    dense_tiled_max_rows is opened, the LDS-tiled kernel of this build."""
     if x.shape[0] == 0:  # a step of unfinished prompt chunks samples nothing
         return x.new_empty((0, w.N))
     if w.w8_t is not None:  # W8A8
@@ -139,12 +140,31 @@ def linear(x: torch.Tensor, w: "Weight", bias: Optional[torch.Tensor] = None) ->
     if x.shape[0] <= 64 and x.is_cuda:
         if w.packed is not None:
             return torch.ops._C_amd.skinny_linear_packed(x, w.packed, bias, w.N, w.K)
-    elif (x.shape[0] <= _STREAM_GEMM_MAX_ROWS and x.is_cuda and w.packed is not None and x.stride(1) == 1
-          and (w.K >= 8192 or (x.shape[0] <= 128 and w.N <= 8192))):
+    elif _takes_stream(x, w):
         # 65..256 rows: X through LDS, one pass over the packed weights -- where it beats the library
         # (tools/bench_stream_gemm.py, M = 128: down 37 vs 76 us, o 21 vs 24, qkv 26 vs 27; not gate_up: 59 vs 55)
         return torch.ops._C_amd.stream_linear_packed(x, w.packed, bias, w.N, w.K)
+    elif _takes_tiled(x, w):
+        return torch.ops._C_amd.linear_tiled(x, w.packed, bias, w.N, w.K, 0)
     return F.linear(x, w.w, bias)
+
+
+def _takes_stream(x: torch.Tensor, w: "Weight") -> bool:
+    return (64 < x.shape[0] <= _STREAM_GEMM_MAX_ROWS and x.is_cuda and w.packed is not None and x.stride(1) == 1
+            and (w.K >= 8192 or (x.shape[0] <= 128 and w.N <= 8192)))
+
+
+def _takes_tiled(x: torch.Tensor, w: "Weight") -> bool:
+    """More than 64 rows of a packed 16-bit weight that the streaming kernel does not claim, inside tuning
+    dense_tiled_min_rows .. dense_tiled_max_rows (shut by default) and the envelope of lvllm_tiled_gemm: the LDS-tiled
+    kernel of this build (csrc/dense_tiled_gemm.hip) instead of the library GEMM."""
+    M = x.shape[0]
+    if M <= 64 or w.packed is None or not x.is_cuda or _takes_stream(x, w):
+        return False
+    get = torch.ops._C_amd.get_tuning
+    return (M <= get("dense_tiled_max_rows") and M >= get("dense_tiled_min_rows") and x.dtype == w.packed.dtype
+            and x.stride(1) == 1 and x.stride(0) % 8 == 0 and x.data_ptr() % 16 == 0
+            and ((M - 1) * x.stride(0) + w.K) * 2 < (1 << 31))
 
 
 _CALIBRATING = False
@@ -421,6 +441,9 @@ class DecoderModel:
                 # gate_up projection with silu_and_mul in its epilogue: one launch, no [T, 2 inter] round trip
                 act = torch.ops._C_amd.skinny_linear_packed_swiglu(hidden, lw.gate_up.packed, None,
                                                                    lw.gate_up.N, lw.gate_up.K)
+            elif lw.gate_up.N % 32 == 0 and not _CALIBRATING and _takes_tiled(hidden, lw.gate_up):
+                # prefill rows inside the tiled range: silu_and_mul in the GEMM's epilogue (bit-identical to the two)
+                act = torch.ops._C_amd.linear_tiled(hidden, lw.gate_up.packed, None, lw.gate_up.N, lw.gate_up.K, 2)
             else:
                 gate_up = linear(hidden, lw.gate_up)
                 act = torch.empty(T, cfg.intermediate_size, dtype=gate_up.dtype, device=gate_up.device)

@@ -5,7 +5,8 @@ attention -> output projection -> add & LayerNorm -> GELU MLP -> add & LayerNorm
 
 Attention is this package's HIP varlen kernel (AttentionType.ENCODER); the residual add and the LayerNorm
 behind it are one launch (`_C_amd.add_layer_norm`; the reference leaves both to torch),
-exact GELU is an in-place kernel of this package too; the projections are library GEMMs (prompt batches are hundreds to thousands of rows).
+exact GELU is an in-place kernel of this package too; the projections are library GEMMs (prompt batches are hundreds to thousands of rows),
+or, with `EncoderConfig.tiled_mlp` inside the opened row range, the MLP's two are this package's LDS-tiled GEMM with bias + GELU / bias in its epilogue.
 Weights are random-initialised: no checkpoint is available offline."""
 from dataclasses import dataclass
 from typing import List
@@ -33,6 +34,10 @@ class EncoderConfig:
     # intermediate [rows, intermediate] is still in the L2s / the Infinity Cache when GELU and fc2 read it instead of
     # making two round trips through HBM (134 MB each way at 16 384 tokens); 0 = one pass over all tokens
     mlp_block_tokens: int = 0
+    # the MLP on the LDS-tiled GEMM of this build (csrc/dense_tiled_gemm.hip) for row counts inside tuning
+    # dense_tiled_min_rows .. dense_tiled_max_rows: fc1 + bias + GELU is one launch, fc2 + bias another, no separate
+    # activation pass over [rows, intermediate]; fc1_w / fc2_w are packed once at load
+    tiled_mlp: bool = False
 
     @property
     def head_dim(self) -> int:
@@ -83,6 +88,11 @@ class EncoderModel:
                        (0.02 * torch.randn(cfg.hidden_size, generator=gen, device=self.device)).to(cfg.dtype))
         self.layers: List[EncoderLayerWeights] = [EncoderLayerWeights(cfg, self.device, gen)
                                                   for _ in range(cfg.num_hidden_layers)]
+        self.tiled_mlp = (cfg.tiled_mlp and self.device.type == "cuda" and cfg.dtype in (torch.bfloat16, torch.float16)
+                          and cfg.hidden_size % 32 == 0 and cfg.intermediate_size % 32 == 0)
+        if self.tiled_mlp:
+            for lw in self.layers:
+                lw.fc1_p, lw.fc2_p = torch.ops._C_amd.pack_weight(lw.fc1_w), torch.ops._C_amd.pack_weight(lw.fc2_w)
         self.backend = PrefillOnlyHIPVarlenBackend(AttentionType.ENCODER)
         self.attn = self.backend.get_impl_cls()(cfg.num_attention_heads, cfg.head_dim, cfg.head_dim ** -0.5,
                                                 cfg.num_attention_heads, None, None, "auto")
@@ -103,6 +113,15 @@ class EncoderModel:
                 return out
             return F.layer_norm(a if b is None else a + b, (hid,), ln[0], ln[1], eps)
 
+        def tiled_rows(n):  # row counts whose MLP takes the tiled GEMM
+            get = torch.ops._C_amd.get_tuning
+            return self.tiled_mlp and n <= get("dense_tiled_max_rows") and n >= get("dense_tiled_min_rows")
+
+        def mlp_tiled(lw, xb):  # fc1 + bias + GELU in one launch, fc2 + bias in another
+            inter = cfg.intermediate_size
+            hb = torch.ops._C_amd.linear_tiled(xb, lw.fc1_p, lw.fc1_b, inter, hid, 1)
+            return torch.ops._C_amd.linear_tiled(hb, lw.fc2_p, lw.fc2_b, hid, inter, 0)
+
         x = add_ln(x, None, self.emb_ln)
         for lw in self.layers:
             qkv = F.linear(x, lw.qkv_w, lw.qkv_b)
@@ -113,12 +132,17 @@ class EncoderModel:
             if blk > 0 and x.shape[0] > blk:
                 y = torch.empty_like(x)
                 for r0 in range(0, x.shape[0], blk):
+                    if tiled_rows(min(blk, x.shape[0] - r0)):
+                        y[r0:r0 + blk] = mlp_tiled(lw, x[r0:r0 + blk])
+                        continue
                     hb = F.linear(x[r0:r0 + blk], lw.fc1_w, lw.fc1_b)
                     if fused and hb.numel() % 8 == 0:
                         torch.ops._C_amd.gelu(hb, hb)
                     else:
                         hb = F.gelu(hb)
                     torch.addmm(lw.fc2_b, hb, lw.fc2_w.t(), out=y[r0:r0 + blk])
+            elif tiled_rows(x.shape[0]):
+                y = mlp_tiled(lw, x)
             else:
                 h = F.linear(x, lw.fc1_w, lw.fc1_b)
                 if fused and h.numel() % 8 == 0:
