@@ -708,6 +708,32 @@ int lvllm_gemm_w4a8_mxfp4(void* y, const void* x_fp8, const void* w_packed, cons
                           const void* bias, int M, int N, int K, int64_t ldx, int dtype, void* workspace,
                           int64_t workspace_bytes, void* stream);
 
+/* ---- Block-scaled W8A8 fp8 (csrc/fp8_block_quant.hip, csrc/fp8_block_gemm.hip) -----------------------------------
+ * The DeepSeek-V3 / Qwen3 "-FP8" checkpoint format: e4m3fn weights wq [N, K] with one fp32 scale per 128 x 128 block,
+ * ws [ceil(N/128), K/128]; e4m3fn activations with one fp32 scale per token and 128 input channels, xs [M, K/128].
+ * lvllm_per_token_group_fp8_quant: x [M, K] bf16 / f16 (rows ldx ELEMENTS apart, ldx % 8 == 0, 16-byte aligned),
+ * K % 128 == 0 -> xq [M, K] e4m3fn and xs [M, K/128], both contiguous.  Per group, in fp32: s = fmaxf(absmax, 1e-10f)
+ * / 448.0f, xq = e4m3(fmaxf(-448, fminf(x / s, 448))), round to nearest even; a NaN comes out as +448 and does not
+ * enter the absmax.
+ * lvllm_fp8_block_pack: once, after loading -- a pure permutation of the N * K bytes into [N/16][K/128][lane 64][32
+ * bytes]: lane (g, c) of unit (t, s) holds wq[16 t + c][128 s + 16 g .. + 15] in its low 16 bytes and
+ * wq[16 t + c][128 s + 64 + 16 g .. + 15] in its high 16.  N % 16 == 0, K % 128 == 0, K < 131072, N * K < 2^32 - 16,
+ * 16-byte aligned tensors; 3 outside the envelope.
+ * lvllm_skinny_gemm_w8a8_fp8_block: y [M, N] = T(sum_b xs[m, b] * ws[n/128, b] * (sum over k of block b of xq[m, k] *
+ * wq[n, k]) + bias[n]): per block the fp32 sum of the MFMA, the product of the two scales in fp32, one fma into the
+ * running sum; the bias added in fp32, one rounding to T = bf16 / f16.  xq [M <= 64, K] (rows ldx BYTES apart, ldx % 16
+ * == 0, 16-byte aligned), w_packed of lvllm_fp8_block_pack, xs / ws contiguous fp32, bias [N] of T or null.  Returns 3
+ * and launches nothing outside the envelope.  workspace: fp32 split-K partials,
+ * lvllm_skinny_gemm_w8a8_fp8_block_workspace_bytes(M, N, K) bytes (0 up to K = 4096), 16-byte aligned; the partials
+ * are summed in the order of the splits. */
+int lvllm_per_token_group_fp8_quant(void* xq, float* xs, const void* x, int64_t M, int K, int64_t ldx, int dtype,
+                                    void* stream);
+int lvllm_fp8_block_pack(void* w_packed, const void* wq, int N, int K, void* stream);
+int64_t lvllm_skinny_gemm_w8a8_fp8_block_workspace_bytes(int M, int N, int K);
+int lvllm_skinny_gemm_w8a8_fp8_block(void* y, const void* xq, const void* w_packed, const float* xs, const float* ws,
+                                     const void* bias, int M, int N, int K, int64_t ldx, int dtype, void* workspace,
+                                     int64_t workspace_bytes, void* stream);
+
 /* ---- device queries (csrc/cuda_utils.h, torch_bindings.cpp:271-279) ------- */
 int64_t lvllm_get_device_attribute(int64_t attribute, int64_t device_id);
 int64_t lvllm_get_max_shared_memory_per_block_device_attribute(int64_t device_id);

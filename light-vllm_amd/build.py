@@ -39,6 +39,8 @@ HIP_SOURCES = [
     "fp8_tiled_gemm.hip",
     "mxfp4_gemm.hip",
     "mxfp4_tiled_gemm.hip",
+    "fp8_block_gemm.hip",
+    "fp8_block_quant.hip",
     "prefill_attention.hip",
     "prepare_inputs.hip",
     "fp8_quant.hip",

@@ -1612,6 +1612,86 @@ torch::Tensor linear_w4a8_mxfp4_tiled(const torch::Tensor& x_fp8, const torch::T
   return mxfp4_linear(x_fp8, w_packed, e_packed, x_scale, N, K, bias, out_dtype, "linear_w4a8_mxfp4_tiled", true);
 }
 
+// ---- block-scaled W8A8 fp8 (csrc/fp8_block_quant.hip, csrc/fp8_block_gemm.hip): e4m3fn weights with one fp32 scale
+// per 128 x 128 block, e4m3fn activations with one fp32 scale per token and 128 input channels
+std::tuple<torch::Tensor, torch::Tensor> per_token_group_fp8_quant(const torch::Tensor& x_in) {
+  LV_CHECK_DEVICE(x_in);
+  TORCH_CHECK(x_in.dim() == 2 && x_in.size(1) > 0 && x_in.size(1) % 128 == 0 &&
+                  (x_in.scalar_type() == at::kHalf || x_in.scalar_type() == at::kBFloat16),
+              "per_token_group_fp8_quant: x must be [M, K] f16 / bf16 with K % 128 == 0");
+  const int64_t M = x_in.size(0), K = x_in.size(1);
+  TORCH_CHECK(K < ((int64_t)1 << 31), "per_token_group_fp8_quant: K too large");
+  const bool strided_ok = x_in.stride(1) == 1 && x_in.stride(0) >= K && x_in.stride(0) % 8 == 0 &&
+                          ((uintptr_t)x_in.data_ptr() & 15) == 0;
+  const torch::Tensor x = strided_ok ? x_in : x_in.contiguous();
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(device_of(x));
+  auto xq = torch::empty({M, K}, x.options().dtype(at::kFloat8_e4m3fn));
+  auto xs = torch::empty({M, K / 128}, x.options().dtype(torch::kFloat));
+  check(lvllm_per_token_group_fp8_quant(xq.data_ptr(), xs.data_ptr<float>(), x.data_ptr(), M, (int)K, x.stride(0),
+                                        dtype_code(x, "per_token_group_fp8_quant"), current_stream(x)));
+  return {xq, xs};
+}
+
+torch::Tensor fp8_block_pack(const torch::Tensor& wq) {
+  LV_CHECK_DEVICE(wq);
+  TORCH_CHECK(wq.dim() == 2 && wq.is_contiguous() && wq.element_size() == 1,
+              "fp8_block_pack: contiguous float8_e4m3fn (or uint8) weight [N, K]");
+  const int64_t N = wq.size(0), K = wq.size(1);
+  TORCH_CHECK(N > 0 && N % 16 == 0 && K > 0 && K % 128 == 0 && K < 131072 && N * K < ((int64_t)1 << 32) - 16,
+              "fp8_block_pack: N % 16 == 0, K % 128 == 0, K < 131072, N * K < 2^32 - 16");
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(device_of(wq));
+  auto w = torch::empty({N * K}, wq.options());
+  check(lvllm_fp8_block_pack(w.data_ptr(), wq.data_ptr(), (int)N, (int)K, current_stream(wq)));
+  return w;
+}
+
+// y [M, N] = T(sum_b xs[m, b] * ws[n/128, b] * (xq . W^T over block b)[m, n] + bias[n]) from the packed weight, any
+// M >= 1: the streaming kernel runs over chunks of 64 rows (row for row the <= 64 result; the weights stream once per
+// chunk)
+torch::Tensor skinny_linear_w8a8_fp8_block(const torch::Tensor& x_in, const torch::Tensor& w_packed,
+                                           const torch::Tensor& xs_in, const torch::Tensor& ws_in, int64_t N, int64_t K,
+                                           const std::optional<torch::Tensor>& bias, at::ScalarType out_dtype) {
+  const char* op = "skinny_linear_w8a8_fp8_block";
+  LV_CHECK_DEVICE(x_in);
+  LV_CHECK_DEVICE(w_packed);
+  LV_CHECK_DEVICE(xs_in);
+  LV_CHECK_DEVICE(ws_in);
+  TORCH_CHECK(x_in.dim() == 2 && x_in.size(1) == K && x_in.scalar_type() == at::kFloat8_e4m3fn, op,
+              ": xq must be [M, K] float8_e4m3fn");
+  TORCH_CHECK(N > 0 && K > 0 && N < ((int64_t)1 << 31) && K < 131072 && N % 16 == 0 && K % 128 == 0 &&
+                  N * K < ((int64_t)1 << 32) - 16,
+              op, ": N % 16 == 0, K % 128 == 0, K < 131072, N * K < 2^32 - 16");
+  TORCH_CHECK(w_packed.is_contiguous() && w_packed.element_size() == 1 && w_packed.numel() == N * K, op,
+              ": w_packed does not have the size fp8_block_pack gives for this N, K");
+  const int64_t M = x_in.size(0), B = K / 128;
+  TORCH_CHECK(xs_in.scalar_type() == at::kFloat && xs_in.dim() == 2 && xs_in.size(0) == M && xs_in.size(1) == B &&
+                  ws_in.scalar_type() == at::kFloat && ws_in.dim() == 2 && ws_in.size(0) == (N + 127) / 128 &&
+                  ws_in.size(1) == B,
+              op, ": xs must be float32 [M, K/128] and ws float32 [ceil(N/128), K/128]");
+  TORCH_CHECK(out_dtype == at::kHalf || out_dtype == at::kBFloat16, op, ": the output is f16 or bf16");
+  TORCH_CHECK(!bias || (bias->is_cuda() && bias->is_contiguous() && bias->numel() == N && bias->scalar_type() == out_dtype),
+              op, ": bias must be [N] of the output's dtype");
+  auto y = torch::empty({M, N}, x_in.options().dtype(out_dtype));
+  if (M == 0) return y;
+  const torch::Tensor xs = xs_in.contiguous(), ws = ws_in.contiguous();
+  const bool strided_ok = x_in.stride(1) == 1 && x_in.stride(0) >= K && x_in.stride(0) % 16 == 0 &&
+                          ((uintptr_t)x_in.data_ptr() & 15) == 0;
+  const torch::Tensor x = strided_ok ? x_in : x_in.contiguous();
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(device_of(x));
+  const int64_t ws_bytes = lvllm_skinny_gemm_w8a8_fp8_block_workspace_bytes((int)std::min<int64_t>(M, 64), (int)N, (int)K);
+  torch::Tensor work;
+  if (ws_bytes > 0) work = torch::empty({ws_bytes / 4}, x.options().dtype(torch::kFloat));
+  const int dt = out_dtype == at::kBFloat16 ? LVLLM_BF16 : LVLLM_F16;
+  for (int64_t m0 = 0; m0 < M; m0 += 64) {
+    const int64_t rows = std::min<int64_t>(64, M - m0);
+    check(lvllm_skinny_gemm_w8a8_fp8_block((char*)y.data_ptr() + m0 * N * 2, (const char*)x.data_ptr() + m0 * x.stride(0),
+                                           w_packed.data_ptr(), xs.data_ptr<float>() + m0 * B, ws.data_ptr<float>(),
+                                           bias ? bias->data_ptr() : nullptr, (int)rows, (int)N, (int)K, x.stride(0), dt,
+                                           ws_bytes > 0 ? work.data_ptr() : nullptr, ws_bytes, current_stream(x)));
+  }
+  return y;
+}
+
 int64_t get_device_attribute(int64_t attribute, int64_t device_id) {
   return lvllm_get_device_attribute(attribute, device_id);
 }
@@ -1766,6 +1846,14 @@ TORCH_LIBRARY(_C_amd, amd) {
   amd.def("linear_w4a8_mxfp4_tiled(Tensor x_fp8, Tensor w_packed, Tensor e_packed, Tensor x_scale, int N, int K, "
           "Tensor? bias, ScalarType out_dtype) -> Tensor");
   amd.impl("linear_w4a8_mxfp4_tiled", torch::kCUDA, &linear_w4a8_mxfp4_tiled);
+  // block-scaled W8A8 fp8: the per-token-group activation quantiser, the load-time permutation, the streaming GEMM
+  amd.def("per_token_group_fp8_quant(Tensor x) -> (Tensor, Tensor)");
+  amd.impl("per_token_group_fp8_quant", torch::kCUDA, &per_token_group_fp8_quant);
+  amd.def("fp8_block_pack(Tensor wq) -> Tensor");
+  amd.impl("fp8_block_pack", torch::kCUDA, &fp8_block_pack);
+  amd.def("skinny_linear_w8a8_fp8_block(Tensor xq, Tensor w_packed, Tensor xs, Tensor ws, int N, int K, "
+          "Tensor? bias, ScalarType out_dtype) -> Tensor");
+  amd.impl("skinny_linear_w8a8_fp8_block", torch::kCUDA, &skinny_linear_w8a8_fp8_block);
   // W8A8 fp8 for prefill batches: activations already fp8 (scaled_fp8_quant), the decode kernel's packed weight
   amd.def("linear_w8a8_fp8_tiled(Tensor x_fp8, Tensor w_packed, Tensor x_scale, Tensor w_scale, int N, int K, "
           "Tensor? bias, ScalarType out_dtype) -> Tensor");

@@ -44,6 +44,8 @@ class ModelConfig:
     # accumulation); the lm_head stays 16-bit
     # "mxfp4": W4A8 projections (OCP MXFP4 weights: e2m1 with one E8M0 scale per 32 input channels; dynamic per-token
     # fp8 activations; the gfx950 scaled MFMA); the lm_head stays 16-bit
+    # "fp8_block": block-scaled W8A8 fp8 projections (e4m3fn weights with one fp32 scale per 128 x 128 block, dynamic
+    # fp8 activations with one scale per token and 128 input channels); the lm_head stays 16-bit
     quantization: Optional[str] = None
     awq_group_size: int = 128
     # W8A8 decode steps: activations quantised once by their producer (norm launches, SwiGLU epilogue) and handed to

@@ -23,7 +23,8 @@ class Weight:
     Twice the bytes; sized for 288 GB of HBM."""
 
     __slots__ = ("w", "packed", "N", "K", "w8_t", "w8_packed", "w_scale", "x_scale", "x_absmax", "awq", "w4_packed",
-                 "w4_meta", "i8", "i8_packed", "i8_scale", "mx4", "mx4_packed", "mx4_scale")
+                 "w4_meta", "i8", "i8_packed", "i8_scale", "mx4", "mx4_packed", "mx4_scale", "f8b", "f8b_packed",
+                 "f8b_scale")
 
     def __init__(self, w: torch.Tensor, pack: bool = True):
         self.w = w
@@ -36,6 +37,8 @@ class Weight:
         self.i8 = self.i8_packed = self.i8_scale = None  # W8A8 int8: row-major OR packed weight, per-channel scales
         # W4A8 MXFP4: row-major OR packed e2m1 codes, and the E8M0 block scales in the same order as the codes
         self.mx4 = self.mx4_packed = self.mx4_scale = None
+        # block-scaled W8A8 fp8: row-major OR packed e4m3fn weight, one fp32 scale per 128 x 128 block
+        self.f8b = self.f8b_packed = self.f8b_scale = None
 
     def numel(self) -> int:
         return self.N * self.K
@@ -48,6 +51,8 @@ class Weight:
             return self.numel() + self.i8_scale.numel() * self.i8_scale.element_size()
         if self.mx4_scale is not None:
             return self.numel() // 2 + self.numel() // 32
+        if self.f8b_scale is not None:
+            return self.numel() + self.f8b_scale.numel() * self.f8b_scale.element_size()
         return self.numel() * (1 if self.w8_t is not None else self.w.element_size())
 
     @staticmethod
@@ -100,6 +105,23 @@ class Weight:
             self.mx4, self.mx4_scale = codes, scales
         self.w = self.packed = None
 
+    @staticmethod
+    def fp8_block_ok(N: int, K: int) -> bool:
+        """The envelope of the block-scaled W8A8 fp8 streaming kernel (lvllm_skinny_gemm_w8a8_fp8_block)."""
+        return N % 16 == 0 and K % 128 == 0 and K < 131072 and N * K < (1 << 32) - 16
+
+    def quantize_fp8_block(self) -> None:
+        """e4m3fn weights with one fp32 scale per 128 x 128 block (quantization/fp8_block.py); the 16-bit copies are
+        dropped.  Inside the kernel's envelope only the packed weight is kept, otherwise the row-major one for the
+        dequantising fallback."""
+        from ..quantization import pack_fp8_block_weight, quantize_fp8_block_weight
+        wq, self.f8b_scale = quantize_fp8_block_weight(self.w)
+        if self.fp8_block_ok(self.N, self.K):
+            self.f8b_packed = pack_fp8_block_weight(wq)
+        else:
+            self.f8b = wq
+        self.w = self.packed = None
+
     def quantize_fp8(self) -> None:
         """Per-tensor e4m3 weights + the calibrated static activation scale; the 16-bit copies are
         dropped (fp8.py:196-239 of the reference quantises at load time the same way)."""
@@ -134,6 +156,10 @@ def linear(x: torch.Tensor, w: "Weight", bias: Optional[torch.Tensor] = None) ->
         from ..quantization import apply_mxfp4_linear
         return apply_mxfp4_linear(x, w.mx4_packed if w.mx4_packed is not None else w.mx4, w.mx4_scale, w.N, w.K,
                                   bias=bias)
+    if w.f8b_scale is not None:  # block-scaled W8A8 fp8: per-token-group fp8 activations, then the streaming kernel
+        from ..quantization import apply_fp8_block_linear
+        return apply_fp8_block_linear(x, w.f8b_packed if w.f8b_packed is not None else w.f8b, w.f8b_scale, w.N, w.K,
+                                      bias=bias)
     if _CALIBRATING:
         m = x.detach().abs().amax()
         w.x_absmax = m if w.x_absmax is None else torch.maximum(w.x_absmax, m)
@@ -245,6 +271,14 @@ class DecoderModel:
                 for w in (l.qkv, l.o, l.gate_up, l.down):
                     if w.w.is_cuda and w.K % 32 == 0:
                         w.quantize_mxfp4()
+            torch.cuda.empty_cache()
+        elif cfg.quantization == "fp8_block":
+            # the four projections of every layer; each quantises its own input per token and 128 channels
+            # (per_token_group_fp8_quant), the lm_head stays 16-bit
+            for l in self.layers:
+                for w in (l.qkv, l.o, l.gate_up, l.down):
+                    if w.w.is_cuda:
+                        w.quantize_fp8_block()
             torch.cuda.empty_cache()
         elif cfg.quantization is not None:
             raise ValueError(f"unsupported quantization {cfg.quantization!r}")

@@ -552,6 +552,66 @@ def mxfp4_prefill_leg(out_path):
             f.write("\n".join(lines) + "\n")
 
 
+def fp8_block_leg(out_path):
+    """--fp8-block [out.md]: the block-scaled W8A8 fp8 launch (skinny_linear_w8a8_fp8_block on activations quantised
+    beforehand) against the per-tensor W8A8 launch (skinny_linear_w8a8 on 16-bit activations: the same weight bytes),
+    and the per-token-group quantiser on its own.  The method of --mxfp4: same process, weights rotate through > 1 GB
+    of buffers per format, 5 warm-up launches, REGIONS regions of PER launches, the legs alternating launch by launch;
+    a region's figure is the median of its device-event times, every region is listed."""
+    REGIONS, PER = 5, 40
+    shapes = [("qkv", 6144, 4096), ("o", 4096, 4096), ("gate_up", 28672, 4096), ("down", 4096, 14336)]
+    fmt = lambda r: " ".join(f"{t:.1f}" for t in r)  # noqa: E731
+    med = lambda r: sorted(r)[len(r) // 2]  # noqa: E731
+    lines = ["| shape | M | block us (regions) | per-tensor us (regions) | quant us (regions) | block TB/s | "
+             "per-tensor TB/s | block vs per-tensor |", "|---|---|---|---|---|---|---|---|"]
+    one = torch.ones(1, device=dev)
+    for name, N, K in shapes:
+        w8 = torch.randint(0, 120, (N * K,), device=dev, dtype=torch.uint8)  # both packs permute bytes: any finite ones
+        ws = torch.rand((N + 127) // 128, K // 128, device=dev) * 1e-2 + 1e-3
+        nw = int(1.1e9 // (N * K)) + 1
+        wbs, wts = [w8.clone() for _ in range(nw)], [w8.clone() for _ in range(nw)]
+        for M in (1, 8, 32, 64):
+            x16 = (torch.randn(M, K, device=dev) * 0.5).to(torch.bfloat16)
+            xq, xs = torch.ops._C_amd.per_token_group_fp8_quant(x16)
+            fs = [lambda i: torch.ops._C_amd.skinny_linear_w8a8_fp8_block(xq, wbs[i % nw], xs, ws, N, K, None, torch.bfloat16),
+                  lambda i: torch.ops._C_amd.skinny_linear_w8a8(x16, wts[i % nw], one, one, N, K, None),
+                  lambda i: torch.ops._C_amd.per_token_group_fp8_quant(x16)]
+            for i in range(5):
+                for f in fs:
+                    f(i)
+            torch.cuda.synchronize()
+            regions, it = [[] for _ in fs], 0
+            for _ in range(REGIONS):
+                evs = []
+                for _ in range(PER):
+                    e = [torch.cuda.Event(enable_timing=True) for _ in range(len(fs) + 1)]
+                    e[0].record()
+                    for j, f in enumerate(fs):
+                        f(it)
+                        e[j + 1].record()
+                    evs.append(e)
+                    it += 1
+                torch.cuda.synchronize()
+                for j in range(len(fs)):
+                    regions[j].append(med([e[j].elapsed_time(e[j + 1]) * 1e3 for e in evs]))
+            rb, rt, rq = regions
+            tot = [N * K + ws.numel() * 4 + M * K + xs.numel() * 4 + M * N * 2, N * K + M * K * 2 + M * N * 2]
+            word = "SLOWER beyond" if min(rb) > max(rt) else "faster beyond" if max(rb) < min(rt) else "within"
+            lines.append(f"| {name} {N}x{K} | {M} | {med(rb):.1f} ({fmt(rb)}) | {med(rt):.1f} ({fmt(rt)}) | "
+                         f"{med(rq):.1f} ({fmt(rq)}) | {tot[0] / med(rb) / 1e6:.2f} | {tot[1] / med(rt) / 1e6:.2f} | "
+                         f"{med(rb) / med(rt):.2f}x the time, {word} the spread |")
+            print(lines[-1], flush=True)
+        del wbs, wts
+        torch.cuda.empty_cache()
+    if out_path:
+        with open(out_path, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if len(sys.argv) > 1 and sys.argv[1] == "--fp8-block":
+    fp8_block_leg(sys.argv[2] if len(sys.argv) > 2 else None)
+    sys.exit(0)
+
 if len(sys.argv) > 1 and sys.argv[1] == "--mxfp4-prefill":
     mxfp4_prefill_leg(sys.argv[2] if len(sys.argv) > 2 else None)
     sys.exit(0)
